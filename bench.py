@@ -1,16 +1,18 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the block-DSP hot path on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frames|strips]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frames|strips] [--dump-outputs DIR]
 
 `--gpus N` with no RANK / WORLD_SIZE in the environment launches the N ranks itself (one process per GPU, RCCL rendezvous on 127.0.0.1);
 under torch.distributed.run it uses the ranks it is given.  Rank 0 prints ONE JSON line.
 
 Workload at N = 1 (BASELINE.json configs[1]): batched open-loop ME integer search, 1080p 8-bit, every 64x64 SB of FRAMES source frames
 against REFS reference frames each, search area 16x9 (the preset-8 1080p maximum, Source/Lib/Codec/enc_mode_config.c:325-326; at the default
-CRF 35 the reference's QP modulation shrinks it to 8x4, see pkg.m8_me_settings), inputs resident in HBM.  One "step" = one launch of
-svt_hip_me_fullpel_search_batch over the whole batch.  `value` = M(SB x search position)/s, i.e. one "block" is one candidate position of one
-64x64 SB against one reference = the 85 block SADs of SURVEY 8(d).
+CRF 35 the reference's QP modulation shrinks it to 8x4, see pkg.m8_me_settings), inputs resident in HBM.  One "step" = L back-to-back launches of
+svt_hip_me_fullpel_search_batch over the whole batch, L fixed by the launch time alone (STEP_SIZING_STEPS), so `--steps K` times K equal steps and
+`ms_per_step` is the time of one of them.  `value` = M(SB x search position)/s, i.e. one "block" is one candidate position of one
+64x64 SB against one reference = the 85 block SADs of SURVEY 8(d).  The inputs are seeded: the same arguments give the same inputs in every run.
+`--dump-outputs DIR` writes the SAD / MV tables of the last timed step (with --mode strips: the frame partition's) to DIR/*.npy (dump_tables).
 
 Multi-GPU, both measured in the same run when N > 1:
   * --mode frames (default, `value`): every rank searches its own batch of frames -- the reference's picture-level parallelism, no data-path
@@ -140,6 +142,10 @@ def synth_planes(n, seed):
 
 
 MIN_TIMED_S = 0.3  # every leg is timed over at least this much device time (--steps 20 used to time 9 ms, before the clocks had ramped)
+# The step-timed regions (headline, frame partition) size ONE step as if --steps were this many: a step = as many launches as last >= min_leg_s / STEP_SIZING_STEPS,
+# the same work whatever --steps says, so that --steps K times K such steps and ms_per_step does not depend on K (at --steps 20 the timed region lasts >= min_leg_s).
+STEP_SIZING_STEPS = 20
+DUMP_ROWS = 32768  # --dump-outputs: at most this many (SB, reference) rows of a result table, a fixed seeded sample when there are more (3 x 85 float32 each: 33 MB)
 
 
 def calibrate_launches(torch, fn, steps, min_s, dist=None):
@@ -1238,7 +1244,7 @@ def strip_rows(total_rows, rank, world):
     return lo, lo + base + (1 if rank < rem else 0)
 
 
-def bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle):
+def bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle, dump=None):
     """north_star's frame-partition case: ONE 1080p picture per step, SB-row strips across the ranks, references resident everywhere, all-gather of the tables."""
     aw, ah = (int(v) for v in a.area.split("x"))
     planes = synth_planes(1 + a.refs, 99)            # the same picture on every rank ...
@@ -1278,12 +1284,16 @@ def bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle)
                                                     vp(ws), vp(wm))
                     k = rf * (q1 - q0) * sbs_x + (row - q0) * sbs_x + col
                     checked += must_equal("frame partition sad", g_all[rk, 0, k], ws) + must_equal("frame partition mv", g_all[rk, 1, k], wm)
-    L = calibrate_launches(torch, step, a.steps, a.min_leg_s, dist)  # pictures per step, so that the timed region lasts >= min_leg_s
+    L = calibrate_launches(torch, step, STEP_SIZING_STEPS, a.min_leg_s, dist)  # pictures per step (see STEP_SIZING_STEPS)
 
     def step_l():
         for _ in range(L):
             step()
     wall, dev = time_steps(torch, step_l, a.steps, a.warmup, dist)
+    if dump is not None and rank == 0:  # the picture-wide tables of the last timed step, as the caller of the partition receives them
+        g_last = (gathered if dist is not None else local).cpu().numpy().view(np.uint32).reshape(world if dist is not None else 1, 2, n_pad, 85)
+        rows = [g_last[rk, :, :a.refs * (q1 - q0) * sbs_x] for rk in range(world) for (q0, q1) in [strip_rows(sbs_y, rk, world)]]
+        dump["sad"], dump["mv"] = np.concatenate([r[0] for r in rows]), np.concatenate([r[1] for r in rows])
     t = torch.tensor([wall], dtype=torch.float64, device="cuda")
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1378,7 +1388,7 @@ def bench_filter_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle
         want_l = np.zeros((Hc, Wc), np.uint16)
         oracle.oracle_lr_filter_frame(vp(want_c), Wc, vp(above), vp(below), Wc, vp(want_l), Wc, Wc, Hc, 0, us, vp(units), bd, 1)
         checked += must_equal("strip-partitioned loop restoration", d_lr.cpu().numpy().view(np.uint16).reshape(Hc, Wc), want_l)
-    L = calibrate_launches(torch, step, a.steps, a.min_leg_s, dist)
+    L = calibrate_launches(torch, step, STEP_SIZING_STEPS, a.min_leg_s, dist)
 
     def step_l():
         for _ in range(L):
@@ -1517,6 +1527,18 @@ def bench_c_partition(torch, lib, pkg, stream, a, world, oracle):
     return res
 
 
+def dump_tables(dirname, prefix, sad, mv):
+    """--dump-outputs: the (SB, reference) x 85 tables a caller of the search receives, as DIR/<prefix>_sad.npy and DIR/<prefix>_mv_x.npy / _mv_y.npy (the packed
+    vector split into its two int16 halves) -- all float32, exact (SADs stay below 2**24) -- plus DIR/<prefix>_rows.npy, the index in the full table of every dumped row.
+    Tables of more than DUMP_ROWS rows are sampled: the same seeded choice of rows for the same table size, so two runs with the same arguments compare row for row."""
+    os.makedirs(dirname, exist_ok=True)
+    rows = np.arange(len(sad)) if len(sad) <= DUMP_ROWS else np.sort(np.random.default_rng(20240601).choice(len(sad), DUMP_ROWS, replace=False))
+    mv = mv[rows]
+    out = {"sad": sad[rows], "mv_x": (mv & 0xFFFF).astype(np.uint16).view(np.int16), "mv_y": (mv >> 16).astype(np.uint16).view(np.int16), "rows": rows}
+    for name, arr in out.items():
+        np.save(os.path.join(dirname, "%s_%s.npy" % (prefix, name)), np.ascontiguousarray(arr, dtype=np.float32))
+
+
 def emit(out, a):
     """stdout gets ONE line of at most bench_line.MAX_LINE bytes (what the driver records and parses); the full object -- every leg with its roofline, CPU baseline,
     parity counts, the encoder's per-stage statistics -- goes to bench_detail.json (gpurun_out/ when it exists, else the working directory) and to stderr."""
@@ -1557,6 +1579,8 @@ def main():
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--legs", type=str, default="", help="comma list restricting the per-kernel legs (me, sad, txfm, config3, cdef, lr, hme, session, tf, tpl, tpl1, tfpic, lrstats, cdefchain, lrsearch, cpart, satd): A/B measurements")
     ap.add_argument("--extra", action="store_true", help="also sweep the other search areas / sub_sad and the remaining stages (reported under kernels)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline's last step computed to DIR/<name>.npy (float32; see dump_tables)")
     a = ap.parse_args()
     if a.gpus > 1 and "RANK" not in os.environ:
         self_launch(a)
@@ -1627,13 +1651,15 @@ def main():
             oracle.oracle_me_fullpel_search(vp(planes, int(d["src_off"])), STRIDE, vp(planes, int(d["ref_off"])), STRIDE, int(d["x_origin"]), int(d["y_origin"]), aw, ah, 0,
                                             vp(ws_), vp(wm_))
             me_checked += must_equal("me_fullpel sad", hs[i], ws_) + must_equal("me_fullpel mv", hm[i], wm_)
-    # a "step" = L back-to-back launches over the resident batch (L batches of frames x refs x 510 SBs), L chosen so that the K timed steps last >= min_leg_s
-    L = calibrate_launches(torch, step, a.steps, a.min_leg_s, dist)
+    # a "step" = L back-to-back launches over the resident batch (L batches of frames x refs x 510 SBs), L from the launch time alone (see STEP_SIZING_STEPS)
+    L = calibrate_launches(torch, step, STEP_SIZING_STEPS, a.min_leg_s, dist)
 
     def step_l():
         for _ in range(L):
             step()
     wall, dev = time_steps(torch, step_l, a.steps, a.warmup, dist)
+    if a.dump_outputs and rank == 0 and a.mode == "frames":  # every launch of a step rewrites the same tables: these are the last timed step's
+        dump_tables(a.dump_outputs, "me", d_sad.cpu().numpy().view(np.uint32).reshape(n, 85), d_mv.cpu().numpy().view(np.uint32).reshape(n, 85))
     t = torch.tensor([wall], dtype=torch.float64, device="cuda")
     if dist is not None:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1672,7 +1698,10 @@ def main():
         rf["valu_probe_this_run"] = probe
         rf["valu_cycles_per_inst"] = probe["v_add_xor_pair"]["cycles_per_wave64_inst_at_2.4GHz"]
         rf["valu_frac_vs_this_runs_qsad_rate"] = (n * aw * ah * 4096 / kernel_s) / (probe["v_qsad_pk_u16_u8"]["lane_ops_per_s"] * 16)
-    fp = bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle)
+    fp_dump = {} if (a.dump_outputs and a.mode == "strips") else None
+    fp = bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle, fp_dump)
+    if fp_dump:
+        dump_tables(a.dump_outputs, "strips_me", fp_dump["sad"], fp_dump["mv"])
     if (world > 1 or a.mode == "strips") and not a.pmc_child:
         fp["in_loop_filters"] = bench_filter_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle)
     if not a.pmc_child and (not a.legs or "cpart" in a.legs.split(",")):

@@ -202,10 +202,9 @@ def test_lr_search_plane_hip_walk_forms(be, oracle, case, walk, monkeypatch):
 @pytest.mark.parametrize("case", range(max(len(GPU_CASES), len(DEV_CASES))))
 def test_lr_search_plane_hip(be, oracle, case, group, monkeypatch):
     """svt_hip_lr_search_plane == oracle_lr_search_plane: SSEs, Wiener taps, self-guided parameter set and projection for every unit.  group: the self-guided parameter
-    sets are filtered and projected in groups that share one set of plane buffers (0 = as many as fit 240 MB -- all of them on these planes --, 1 and 3 forced)"""
+    sets are filtered and projected in groups that share one set of plane buffers (0 = as many as fit 240 MB -- all of them on these planes --, 1 and 3 forced; with
+    one set or none a forced group size must leave the result as it is)"""
     cases = GPU_CASES if be.is_gpu else DEV_CASES
-    if group and (case >= len(cases) or not cases[case][6][0] or case in (0, 2, 4)):  # (case 0 has three sets: covered by cases 1 and 5)
-        pytest.skip("grouping only matters with several self-guided parameter sets")
     if group:
         monkeypatch.setenv("SVT_HIP_LR_SG_GROUP", str(group))
     else:

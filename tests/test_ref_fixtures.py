@@ -5,7 +5,7 @@ INSTANTIATE_TEST_SUITE_P(HIP, ...) blocks that pass `svt_*_hip` where the refere
 (__graft_entry__.build()) and travels to the GPU box with the snapshot (oracle/_ref/ is git-ignored, not gpurun-ignored); the `_c` side of every comparison is
 oracle/_ref/libsvtref.so = the reference compiled in place.
 
-  -m gpu      : every HIP-instantiated suite on the MI355X through svt-av1-psy_amd/libsvtav1_hip.so, sharded over the host's cores with gtest's own sharding
+  -m gpu      : every HIP-instantiated suite on the MI355X through svt-av1-psy_amd/libsvtav1_hip.so, in GPU_SHARDS processes with gtest's own sharding
   -m "not gpu": the same objects linked with the CPU interpreter build of the kernel sources -- the suite list is checked and a slice small enough for it runs
 """
 import json
@@ -49,6 +49,7 @@ SUITES = {
 FULL = os.environ.get("SVT_HIP_FIXTURES") == "full"
 FILTER = "HIP*" if FULL else "HIP*:-HIPFULL*:*.MultipleQ/*"
 FULL_ONLY = {"HIPFULL/CDEFFindDirTest": 1, "HIPFULL/CDEFFindDirDualTest": 1}
+GPU_SHARDS = 4  # gtest processes side by side on the one MI355X
 
 
 def _list(binary):
@@ -110,8 +111,10 @@ def _run_sharded(binary, gtest_filter, shards, timeout):
 def test_reference_fixtures_on_the_hip_symbols():
     assert os.path.isfile(BIN_GPU), "oracle/_ref/fixtures/SvtAv1HipFixtures is missing: __graft_entry__.build() makes it where /root/reference exists, and it ships with the snapshot"
     total = _check_suite_list(BIN_GPU)
-    shards = max(2, min(24, (os.cpu_count() or 4)))
-    tests, failures, failed = _run_sharded(BIN_GPU, FILTER, shards, timeout=2400 if FULL else 900)
+    # every shard opens the device, next to this process which already has it open: GPU_SHARDS + 1 processes hold it at once, whatever the host's core count.
+    # (More shards buy little: the per-call `_hip` round trips of the shards queue on the one device -- profiles/r06_small_call_zero_copy.txt against the 24-shard run.)
+    shards = GPU_SHARDS
+    tests, failures, failed = _run_sharded(BIN_GPU, FILTER, shards, timeout=2400 if FULL else 1800)
     assert failures == 0, failed[:40]
     assert tests >= total, (tests, total)
 
