@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the block-DSP hot path on MI355X (contract: see the task statement / DESIGN.md section 6).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frames|strips] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--mode frames|strips] [--dump-outputs DIR] [--full]
+
+A plain run does what its headline needs and nothing else: it makes the inputs, warms up, times the K steps, writes --dump-outputs and prints the line (`value`,
+`ms_per_step`, the roofline arithmetic of the timed launches).  Everything else this file measures or checks is behind `--full`: the in-run comparisons with the CPU
+checker, the counter passes, the VALU rate probe, the per-kernel legs (and `--legs` / `--extra`, which select among them), the frame partition next to a frames-mode
+headline, the library's own partition, the CPU baselines and the encoder runs.  The timed steps and their inputs are the same with and without `--full`.
 
 `--gpus N` with no RANK / WORLD_SIZE in the environment launches the N ranks itself (one process per GPU, RCCL rendezvous on 127.0.0.1);
 under torch.distributed.run it uses the ranks it is given.  Rank 0 prints ONE JSON line.
@@ -14,14 +19,14 @@ svt_hip_me_fullpel_search_batch over the whole batch, L fixed by the launch time
 64x64 SB against one reference = the 85 block SADs of SURVEY 8(d).  The inputs are seeded: the same arguments give the same inputs in every run.
 `--dump-outputs DIR` writes the SAD / MV tables of the last timed step (with --mode strips: the frame partition's) to DIR/*.npy (dump_tables).
 
-Multi-GPU, both measured in the same run when N > 1:
+Multi-GPU, both measured in the same run with --full or --mode strips (a plain frames-mode run times the first alone):
   * --mode frames (default, `value`): every rank searches its own batch of frames -- the reference's picture-level parallelism, no data-path
     collective, "weak" scaling;
   * frame partition (`frame_partition` object; `value` with --mode strips): ONE picture per step cut into contiguous SB-row strips
     (1080p: 17 rows -> 3,2,2,2,2,2,2,2 at N = 8), reference planes resident on every GPU (broadcast once, outside the timed region), every rank
     searches its strip against all references, the per-strip 85 x (SAD, MV) tables are all-gathered over RCCL -- "strong" scaling.
 
-Before a leg is timed its output is compared with the CPU checker on a slice (oracle/ = test infrastructure, used here only as the checker
+With --full, before a leg is timed its output is compared with the CPU checker on a slice (oracle/ = test infrastructure, used here only as the checker
 and for the `cpu_baseline` legs); a mismatch aborts the run.  Extra objects on the JSON line: `roofline` (dominant kernel, algorithmic bytes of
 SURVEY 8(d) / event-timed kernel duration, against the 8 TB/s HBM peak and against the 6.3 TB/s copy ceiling of MI355X_MICROARCH.md),
 `cpu_baseline` (the reference's own AVX2 kernels from oracle/_ref on the host cores, bounded sample) and `kernels` (the other primitives of
@@ -1581,13 +1586,19 @@ def main():
     ap.add_argument("--extra", action="store_true", help="also sweep the other search areas / sub_sad and the remaining stages (reported under kernels)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps write what the headline's last step computed to DIR/<name>.npy (float32; see dump_tables)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: parity checks, counter passes, per-kernel legs, frame partition, CPU baselines, encoder fps")
     a = ap.parse_args()
+    if (a.legs or a.extra) and not (a.full or a.pmc_child):
+        ap.error("--legs and --extra select among the legs of a --full run: give --full with them")
     if a.gpus > 1 and "RANK" not in os.environ:
         self_launch(a)
     global NO_CHECK, LIVE_PMC
-    if a.pmc_child:  # one of live_pmc()'s passes: every GPU leg of the default line, a few launches each, no CPU legs, no checks, no nested PMC
-        a.no_cpu = a.no_parity_check = a.no_pmc = True
+    if a.pmc_child:  # one of live_pmc()'s passes: every GPU leg of the --full line, a few launches each, no CPU legs, no checks, no nested PMC
+        a.no_cpu = a.no_parity_check = a.no_pmc = a.full = True
         a.steps, a.warmup, a.min_leg_s = 3, 1, 0.0
+    if not a.full:  # a plain run: the headline alone -- no checker, no counter passes, no CPU legs (the legs, probes and partitions are gated on a.full below)
+        a.no_cpu = a.no_parity_check = a.no_pmc = True
     NO_CHECK = a.no_parity_check
     if not a.no_pmc and a.gpus == 1 and "RANK" not in os.environ:
         LIVE_PMC = live_pmc(a)  # before this process touches the GPU; None -> fallback to the committed summary
@@ -1679,7 +1690,7 @@ def main():
                   sad_ops_per_s=n * aw * ah * 4096 / kernel_s,
                   # measured v_qsad_pk_u16_u8 issue cost: 22.4 cycles per wave64 instruction per SIMD (profiles/r01_call1_valu_issue_rates.txt)
                   valu_peak_sad_ops_per_s=QSAD_PEAK, valu_frac=n * aw * ah * 4096 / kernel_s / QSAD_PEAK)
-    if not a.pmc_child and rank == 0:
+    if a.full and not a.pmc_child and rank == 0:
         # the denominators of valu_frac, measured in THIS run: lane-operations per second of a kernel that issues nothing but independent
         # v_qsad_pk_u16_u8 / v_add + v_xor instructions on every SIMD -- rates, so no clock has to be assumed; the "cycles" figures divide by the 2.4 GHz the device
         # property reports and are only a unit conversion of those rates
@@ -1698,13 +1709,15 @@ def main():
         rf["valu_probe_this_run"] = probe
         rf["valu_cycles_per_inst"] = probe["v_add_xor_pair"]["cycles_per_wave64_inst_at_2.4GHz"]
         rf["valu_frac_vs_this_runs_qsad_rate"] = (n * aw * ah * 4096 / kernel_s) / (probe["v_qsad_pk_u16_u8"]["lane_ops_per_s"] * 16)
-    fp_dump = {} if (a.dump_outputs and a.mode == "strips") else None
-    fp = bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle, fp_dump)
-    if fp_dump:
-        dump_tables(a.dump_outputs, "strips_me", fp_dump["sad"], fp_dump["mv"])
-    if (world > 1 or a.mode == "strips") and not a.pmc_child:
+    fp = None
+    if a.full or a.mode == "strips":  # (a strips-mode headline IS the frame partition's figure)
+        fp_dump = {} if (a.dump_outputs and a.mode == "strips") else None
+        fp = bench_frame_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle, fp_dump)
+        if fp_dump:
+            dump_tables(a.dump_outputs, "strips_me", fp_dump["sad"], fp_dump["mv"])
+    if a.full and (world > 1 or a.mode == "strips") and not a.pmc_child:
         fp["in_loop_filters"] = bench_filter_partition(torch, lib, pkg, stream, a, dist, rank, world, oracle)
-    if not a.pmc_child and (not a.legs or "cpart" in a.legs.split(",")):
+    if a.full and not a.pmc_child and (not a.legs or "cpart" in a.legs.split(",")):
         # the product's own multi-device path (one process, csrc/partition.hip), while the other ranks wait at the barrier
         if dist is not None:
             dist.barrier()
@@ -1731,11 +1744,11 @@ def main():
         out["config"]["parallelism"] = "SB-row strips of one picture x%d + RCCL all-gather" % world
         out["frames_mode_value"] = value
     kernels = {}
-    cpu = rank == 0 and world == 1 and not a.no_cpu
+    cpu = a.full and rank == 0 and world == 1 and not a.no_cpu
     import bench_legs
     bench_legs.MIN_S = a.min_leg_s
     want = (lambda leg: not a.legs or leg in a.legs.split(","))
-    if not a.only_me:
+    if a.full and not a.only_me:
         if want("me"):  # the same batched search at the areas preset 8 really derives at its default CRF 35 (8 x 4 and 8 x 3: pkg.m8_me_settings): HBM-bound there
             for (w2, h2) in ((8, 4), (8, 3)):
                 dd = np.concatenate([pkg.me_descs_for_frame(W, H, STRIDE, PAD, PAD, w2, h2, PLANE, n_refs=a.refs, src_plane=f, ref_plane0=f + 1) for f in range(a.frames)])
@@ -1844,7 +1857,7 @@ def main():
             if cpu:
                 for name in keep:
                     kernels[name].update(cpu_lr_search(keep[name], budget_s=5.0))
-    if a.extra:
+    if a.full and a.extra:
         for (w2, h2, sub) in [(16, 9, 1), (64, 32, 0), (256, 256, 0)]:
             nf = a.frames if w2 < 64 else (4 if w2 < 256 else 1)
             dd = np.concatenate([pkg.me_descs_for_frame(W, H, STRIDE, PAD, PAD, w2, h2, PLANE, n_refs=(a.refs if w2 < 256 else 1), src_plane=f, ref_plane0=f + 1)
@@ -1896,7 +1909,7 @@ def main():
             out["encoder_fps_4k10_preset8"] = encoder_fps_4k10(1)  # BASELINE configs[4] at one GPU (the N-GPU form: below, rank 0 of a --gpus N run)
     elif rank == 0:
         out["cpu_baseline"] = None
-        if world > 1 and not a.no_cpu and not a.pmc_child and not a.legs and not a.only_me:
+        if a.full and world > 1 and not a.no_cpu and not a.pmc_child and not a.legs and not a.only_me:
             # BASELINE configs[4] on this node's GPUs: the reference encoder with its pictures sharded over SVT_HIP_DEVICES=0..N-1 (the other ranks wait at the barrier below;
             # their GPUs are idle by now).  Identity against the C-only encoder is decided inside; a failure is reported in the object, never raised.
             out["encoder_fps_4k10_preset8"] = encoder_fps_4k10(world)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Condense a rocprofv3 --kernel-trace CSV directory of `bench.py --legs lrsearch` into the launch timeline of one svt_hip_lr_search_plane call per setting
+"""Condense a rocprofv3 --kernel-trace CSV directory of `bench.py --full --legs lrsearch` into the launch timeline of one svt_hip_lr_search_plane call per setting
 (which kernel ran on which queue, when, for how long).  usage: tools/lr_timeline.py <trace_dir> <out.txt>"""
 import csv
 import glob
