@@ -162,16 +162,6 @@ __device__ __forceinline__ void stage_rows_wide_any(uint32_t* lds, int pitch_dw,
     else if (total - base > 0) stage_rows_wide_step<NT, 1>(lds, pitch_dw, g, gstride, width, total, cpr, dr, dc, base, tid, r, c);
 }
 
-// the same with the chunks per row given by the caller (= ceil(width / 16) <= (pitch_dw + 3) / 4): no dead chunks for windows narrower than the LDS pitch
-template <int NT>
-__device__ __forceinline__ void stage_rows_wide_cpr(uint32_t* lds, int pitch_dw, const uint8_t* g, uint32_t gstride, int width, int rows, int cpr, int tid) {
-    const int total = rows * cpr, dr = NT / cpr, dc = NT - dr * cpr;
-    int       r = tid / cpr, c = tid - r * cpr, base = 0;
-    for (; total - base > 2 * NT; base += 4 * NT) stage_rows_wide_step<NT, 4>(lds, pitch_dw, g, gstride, width, total, cpr, dr, dc, base, tid, r, c);
-    if (total - base > NT) stage_rows_wide_step<NT, 2>(lds, pitch_dw, g, gstride, width, total, cpr, dr, dc, base, tid, r, c);
-    else if (total - base > 0) stage_rows_wide_step<NT, 1>(lds, pitch_dw, g, gstride, width, total, cpr, dr, dc, base, tid, r, c);
-}
-
 __device__ __forceinline__ uint32_t dpp_add_quad_xor1(uint32_t v) {
     return v + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0xB1, 0xf, 0xf, false);
 }
@@ -193,17 +183,58 @@ __device__ __forceinline__ uint32_t umin32(uint32_t a, uint32_t b) { return a < 
 constexpr int ME_PITCH = 34; // window row pitch in dwords: >= 17 + 64 / 4, even (8-byte LDS stores) and = 2 mod 8, so the 8 block rows x
                              // 8 block columns a half-wave reads fall into 64 distinct LDS banks (8 * 34 = 16 mod 64)
 
+// 32x32 SADs of four consecutive y steps in one pass (reduce-scatter over the four quads of a 16-lane row, which are exactly the four DPP banks).  In: v[c] = this
+// lane's 16x16 SAD of step c.  Out: the lanes of quad c hold the complete 32x32 SAD of step c (lane q of the quad: x position q).  An all-reduce per step computes
+// every sum four times (8 DPP adds per four steps, and a key + min per step); this is 6 bank-masked adds for all four, then one key + min.
+// row_ror:n = lane l reads lane (l - n) mod 16 of its row: ror:8 is symmetric, ror:12 reads the upper neighbour quad (l + 4), ror:4 the lower one (l - 4).
+__device__ __forceinline__ uint32_t dpp_scatter_sum_quads(const uint32_t (&v)[4]) {
+#ifdef SVT_HIP_EMU
+    const uint32_t a0 = dpp_add_row_ror8(v[0]), a1 = dpp_add_row_ror8(v[1]), a2 = dpp_add_row_ror8(v[2]), a3 = dpp_add_row_ror8(v[3]); // quad Q: v[Q] + v[Q ^ 2]
+    const uint32_t t0 = (uint32_t)__builtin_amdgcn_update_dpp((int)a0, (int)a2, 0xE4, 0xf, 0xc, false); // quads 0,1: step 0 | quads 2,3: step 2
+    const uint32_t t1 = (uint32_t)__builtin_amdgcn_update_dpp((int)a1, (int)a3, 0xE4, 0xf, 0xc, false); // quads 0,1: step 1 | quads 2,3: step 3
+    const uint32_t y  = (uint32_t)__builtin_amdgcn_update_dpp((int)t0, (int)t1, 0xE4, 0xf, 0xa, false); // quads 0,2 keep t0, quads 1,3 take t1
+    const uint32_t x  = y + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t0, 0x12C, 0xf, 0x5, false);  // quads 0,2 += t0 of their upper neighbour
+    return x + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)t1, 0x124, 0xf, 0xa, false);               // quads 1,3 += t1 of their lower neighbour
+#else
+    // The same in six v_add_u32_dpp whose bank mask leaves the other quads of the destination alone -- there is no builtin for an add that keeps its destination
+    // (the compiler turns the form above into 4 adds, 5 moves, 2 zero fills and a v_add3).  A DPP operand needs two wait states after the VALU write of its register
+    // and the compiler does not look into an asm block: hence the s_nop in front (the inputs) and before the last add (t1 was written two instructions earlier).
+    uint32_t t0, t1;
+    asm("s_nop 1\n\t"
+        "v_add_u32_dpp %0, %2, %2 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"  // t0: quads 0,1 = step 0, v[Q] + v[Q ^ 2]
+        "v_add_u32_dpp %0, %4, %4 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"  //     quads 2,3 = step 2
+        "v_add_u32_dpp %1, %3, %3 row_ror:8 row_mask:0xf bank_mask:0x3\n\t"  // t1: quads 0,1 = step 1
+        "v_add_u32_dpp %1, %5, %5 row_ror:8 row_mask:0xf bank_mask:0xc\n\t"  //     quads 2,3 = step 3
+        "v_add_u32_dpp %0, %0, %0 row_ror:12 row_mask:0xf bank_mask:0x5\n\t" // quads 0,2: t0 + t0 of the upper neighbour = steps 0, 2 complete
+        "s_nop 0\n\t"
+        "v_add_u32_dpp %0, %1, %1 row_ror:4 row_mask:0xf bank_mask:0xa"       // quads 1,3: t1 + t1 of the lower neighbour = steps 1, 3 complete
+        : "=&v"(t0), "=&v"(t1)
+        : "v"(v[0]), "v"(v[1]), "v"(v[2]), "v"(v[3]));
+    return t0;
+#endif
+}
+
 // All strips of one wave. keys: 8x8 -> (sad16 << 16) | pos   (one v_lshl_or / v_and_or per position, straight from the packed u16 lanes)
 //                               16x16/32x32/64x64 -> (sad << 11) | pos   (sad64 < 2^20, pos < 2^11)
+// pos = yl * 64 + 4 * g + x.  Inside the loops a key carries only the wave-uniform part of its position (a scalar operand); the part that is a constant of the lane
+// -- x for 16x16, x and the step within the group of four for 32x32 / 64x64 -- occupies disjoint bits and is ORed into the lane's winner once at the end.  Every key
+// a lane compares shares that part, so the order of its keys, and with it "first minimum in raster order", is unchanged.
+// 32x32 and 64x64 are evaluated once per group of four y steps (dpp_scatter_sum_quads): quad c of a row then stands for step c of the group.
 // FULL: the tile width is a multiple of 4, no strip has invalid positions.
 template <bool SUB, bool FULL, int PITCH = ME_PITCH>
 __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ win, const uint32_t (&s)[8][2], int Wt, int Ht, int g0, int gstep, int l,
                                                  uint32_t& best8, uint32_t& best16, uint32_t& best32, uint32_t& best64) {
     const int bx = (l & 1) | ((l >> 1) & 2) | ((l >> 2) & 4);
     const int by = ((l >> 1) & 1) | ((l >> 2) & 2) | ((l >> 3) & 4);
-    const int q  = l & 3;
+    const int q  = l & 3, c = (l >> 2) & 3;
     const int      G    = (Wt + 3) >> 2;
     const uint32_t qsel = 0x0c0c0100u + 0x0202u * (uint32_t)q; // v_perm_b32 selector: u16 number q of {thi:tlo}, zero extended
+    uint32_t       himask = 0xffff0000u; // in a VGPR, so that (x & himask) | pos is one v_and_or_b32 with the scalar pos (VOP3 takes no literal on gfx9)
+    SVT_HIP_OPAQUE_I32(himask);
+    // A step that a last group of fewer than four does not have enters the sums as NO_STEP per lane: its 32x32 sum (4 x) and 64x64 sum (16 x) exceed every real
+    // one (261 120 and 1 044 480) and still fit the 21 bits a key has for the SAD, so its key loses against the key of any step that exists.
+    constexpr uint32_t NO_STEP = 0x1ffffu;
+    uint32_t       b16 = 0xffffffffu, b32 = 0xffffffffu, b64 = 0xffffffffu; // winners with the lane-constant position bits still missing
     for (int g = g0; g < G; g += gstep) {
         const uint32_t* colp   = win + (by * 8) * PITCH + bx * 2 + g;
         const int       nvalid = (Wt - 4 * g) < 4 ? (Wt - 4 * g) : 4;
@@ -217,50 +248,63 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
             ra[r] = *(const U64A4*)(colp + r * PITCH);
             rb[r] = *(const U64A4*)(colp + r * PITCH + 1);
         }
-        uint32_t pos = (uint32_t)(4 * g), posq = (uint32_t)(4 * g + q);
+        uint32_t pos = (uint32_t)(4 * g); // wave-uniform: the keys take it as a scalar operand
         for (int yb = 0; yb < Ht; yb += 8) {
             const uint32_t* rowp = colp + (yb + 7) * PITCH;
 #pragma unroll
-            for (int i = 0; i < 8; i++) {
-                if (yb + i < Ht) {
-                    ra[(i + 7) & 7] = *(const U64A4*)(rowp + i * PITCH);
-                    rb[(i + 7) & 7] = *(const U64A4*)(rowp + i * PITCH + 1);
-                    unsigned long long acc = 0;
+            for (int h = 0; h < 2; h++) { // the unrolled ring block as two groups of four y steps
+                if (yb + 4 * h < Ht) {
+                    uint32_t v[4] = {NO_STEP, NO_STEP, NO_STEP, NO_STEP}; // 16x16 SADs of the group's steps
 #pragma unroll
-                    for (int r = 0; r < 8; r += (SUB ? 2 : 1)) {
-                        acc = __builtin_amdgcn_qsad_pk_u16_u8(ra[(i + r) & 7].v, s[r][0], acc);
-                        acc = __builtin_amdgcn_qsad_pk_u16_u8(rb[(i + r) & 7].v, s[r][1], acc);
+                    for (int j = 0; j < 4; j++) {
+                        const int i = 4 * h + j;
+                        if (yb + i < Ht) {
+                            ra[(i + 7) & 7] = *(const U64A4*)(rowp + i * PITCH);
+                            rb[(i + 7) & 7] = *(const U64A4*)(rowp + i * PITCH + 1);
+                            unsigned long long acc = 0;
+#pragma unroll
+                            for (int r = 0; r < 8; r += (SUB ? 2 : 1)) {
+                                acc = __builtin_amdgcn_qsad_pk_u16_u8(ra[(i + r) & 7].v, s[r][0], acc);
+                                acc = __builtin_amdgcn_qsad_pk_u16_u8(rb[(i + r) & 7].v, s[r][1], acc);
+                            }
+                            if (SUB) acc <<= 1; // 8x4 on even rows, doubled (motion_estimation.c:105-126); u16 lanes cannot carry
+                            const uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
+                            // 8x8: this lane's block, 4 positions
+                            const uint32_t p1 = FULL ? pos + 1 : ((pos + 1) | inv1), p2 = FULL ? pos + 2 : ((pos + 2) | inv2), p3 = FULL ? pos + 3 : ((pos + 3) | inv3);
+                            const uint32_t k0 = (lo << 16) | pos, k1 = (lo & himask) | p1, k2 = (hi << 16) | p2, k3 = (hi & himask) | p3;
+                            best8 = umin32(umin32(best8, k0), k1);
+                            best8 = umin32(umin32(best8, k2), k3);
+                            // 16x16 = the quad's four 8x8 (u16 lanes: 4 * 16320 < 65536, so plain adds never carry)
+                            const uint32_t tlo = dpp_add_quad_xor2(dpp_add_quad_xor1(lo));
+                            const uint32_t thi = dpp_add_quad_xor2(dpp_add_quad_xor1(hi));
+                            // lane q of the quad takes position q from here on
+                            v[j] = __builtin_amdgcn_perm(thi, tlo, qsel);
+                            const uint32_t k16 = (v[j] << KEY_POS_BITS) | pos;
+                            b16 = umin32(b16, FULL ? k16 : (k16 | invq));
+                            pos += ME_TW;
+                        }
                     }
-                    if (SUB) acc <<= 1; // 8x4 on even rows, doubled (motion_estimation.c:105-126); u16 lanes cannot carry
-                    const uint32_t lo = (uint32_t)acc, hi = (uint32_t)(acc >> 32);
-                    // 8x8: this lane's block, 4 positions
-                    uint32_t k0 = (lo << 16) | pos, k1 = (lo & 0xffff0000u) | (pos + 1), k2 = (hi << 16) | (pos + 2),
-                             k3 = (hi & 0xffff0000u) | (pos + 3);
-                    if (!FULL) { k1 |= inv1; k2 |= inv2; k3 |= inv3; }
-                    best8 = umin32(umin32(best8, k0), k1);
-                    best8 = umin32(umin32(best8, k2), k3);
-                    // 16x16 = the quad's four 8x8 (u16 lanes: 4 * 16320 < 65536, so plain adds never carry)
-                    const uint32_t tlo = dpp_add_quad_xor2(dpp_add_quad_xor1(lo));
-                    const uint32_t thi = dpp_add_quad_xor2(dpp_add_quad_xor1(hi));
-                    // lane q of the quad takes position q from here on
-                    const uint32_t sad16 = __builtin_amdgcn_perm(thi, tlo, qsel);
-                    const uint32_t pq    = FULL ? posq : (posq | invq);
-                    best16 = umin32(best16, (sad16 << KEY_POS_BITS) | pq);
-                    // 32x32 = 4 quads of a 16-lane row; 64x64 = 4 rows
-                    const uint32_t sad32 = dpp_add_row_ror8(dpp_add_row_ror4(sad16));
-                    best32 = umin32(best32, (sad32 << KEY_POS_BITS) | pq);
-                    // row sums across the wave with the gfx950 row / half swaps (VALU; a ds_bpermute pair sat in the dependent chain before)
+                    // 32x32 = 4 quads of a 16-lane row, 64x64 = 4 rows: once for the group; quad c now stands for step c
+                    const uint32_t gpos  = (uint32_t)(4 * g + ME_TW * (yb + 4 * h));
+                    const uint32_t sad32 = dpp_scatter_sum_quads(v);
+                    const uint32_t k32   = (sad32 << KEY_POS_BITS) | gpos;
+                    b32 = umin32(b32, FULL ? k32 : (k32 | invq));
+                    // row sums across the wave with the gfx950 row / half swaps: lane-wise, every lane of a row holds a different (step, x)
                     const auto     x16   = __builtin_amdgcn_permlane16_swap(sad32, sad32, false, false);
                     const uint32_t pair  = x16[0] + x16[1];
                     const auto     x32   = __builtin_amdgcn_permlane32_swap(pair, pair, false, false);
                     const uint32_t sad64 = x32[0] + x32[1];
-                    best64 = umin32(best64, (sad64 << KEY_POS_BITS) | pq);
-                    pos += ME_TW;
-                    posq += ME_TW;
+                    const uint32_t k64   = (sad64 << KEY_POS_BITS) | gpos;
+                    b64 = umin32(b64, FULL ? k64 : (k64 | invq));
                 }
             }
         }
     }
+    // the lane-constant position bits: x = q (bits 0-1; 4 * g has none of them), step within the group = c (bits 6-7; the group's first row is a multiple of 4).
+    // A lane that saw no valid position keeps all ones.
+    best16 = umin32(best16, b16 | (uint32_t)q);
+    best32 = umin32(best32, b32 | (uint32_t)(q | (c << 6)));
+    best64 = umin32(best64, b64 | (uint32_t)(q | (c << 6)));
 }
 
 template <bool SUB>
@@ -351,6 +395,58 @@ __device__ __forceinline__ uint32_t dpp_min_quad_xor2(uint32_t v) { return umin3
 __device__ __forceinline__ uint32_t dpp_min_row_ror4(uint32_t v) { return umin32(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124, 0xf, 0xf, false)); }
 __device__ __forceinline__ uint32_t dpp_min_row_ror8(uint32_t v) { return umin32(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128, 0xf, 0xf, false)); }
 
+// The window of one item, staged by its own wave: rows x width bytes (64 <= width < 16 * (NF + 1), any global alignment / stride) into LDS rows of PITCH dwords.
+// NF = full 16-byte chunks per row.  Lane -> (row within a block of RPI = 64 / NF rows, chunk) once; every further chunk of the lane lies RPI rows lower, so the walk
+// is a scalar step on the row base and a compile-time LDS offset: no per-chunk row / column arithmetic, no funnel shift, no zeroing (stage_rows_wide_step pays ~50 VALU
+// per chunk for the general case).  Four loads per lane are in flight before the first LDS store.  The partial chunk of a row (width % 16 bytes) is a pass of its own
+// over the rows: the 16 bytes that END at the row end, shifted down by a wave-uniform byte count and zero filled; its loads are issued first of all.
+// Same contract as stage_rows_u8: nothing outside [row, row + width) is read; every chunk that holds window bytes is written whole, zero filled behind the row end.
+template <int NF, int PITCH>
+__device__ __forceinline__ void stage_window_wave(uint32_t* lds, const uint8_t* g, const uint32_t gstride, const int width, const int rows, const int l) {
+    constexpr int RPI = 64 / NF;
+    const int     rem = width & 15, back = 16 - rem; // bytes of the partial chunk; rows <= 128: two of them per lane at most
+    const bool    p0 = rem != 0 && l < rows, p1 = rem != 0 && l + 64 < rows;
+    u32x4_a1      t[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
+    const uint32_t tail_off = (uint32_t)l * gstride + (uint32_t)(width - 16);
+    if (p0) t[0] = *(const u32x4_a1*)(g + tail_off);
+    if (p1) t[1] = *(const u32x4_a1*)(g + (size_t)64 * gstride + tail_off);
+
+    const int lr = l / NF, lc = l - lr * NF;
+    if (lr < RPI) { // (NF = 5: lanes 60-63 have no chunk)
+        const uint32_t goff = (uint32_t)lr * gstride + (uint32_t)lc * 16u;
+        uint32_t*      lp   = lds + lr * PITCH + lc * 4;
+        for (int r0 = 0; r0 < rows; r0 += 4 * RPI) {
+            const uint8_t* gb = g + (size_t)r0 * gstride; // wave-uniform row base
+            u32x4_a1       v[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (r0 + k * RPI + lr < rows) v[k] = *(const u32x4_a1*)(gb + (size_t)(k * RPI) * gstride + goff);
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (r0 + k * RPI + lr < rows) {
+                    uint32_t* o = lp + (r0 + k * RPI) * PITCH;
+                    *(u32x2_a8*)(o + 0) = u32x2_a8{v[k].x, v[k].y};
+                    *(u32x2_a8*)(o + 2) = u32x2_a8{v[k].z, v[k].w};
+                }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 2; k++)
+        if (k == 0 ? p0 : p1) {
+            uint32_t x0 = t[k].x, x1 = t[k].y, x2 = t[k].z, x3 = t[k].w; // shift the 128-bit value right by `back` bytes, zero fill
+            if (back & 4) { x0 = x1; x1 = x2; x2 = x3; x3 = 0; }
+            if (back & 8) { x0 = x2; x1 = x3; x2 = 0; x3 = 0; }
+            const uint32_t bs = (uint32_t)back & 3u;
+            x0 = __builtin_amdgcn_alignbyte(x1, x0, bs);
+            x1 = __builtin_amdgcn_alignbyte(x2, x1, bs);
+            x2 = __builtin_amdgcn_alignbyte(x3, x2, bs);
+            x3 = __builtin_amdgcn_alignbyte(0u, x3, bs);
+            uint32_t* o = lds + (l + 64 * k) * PITCH + NF * 4;
+            if (NF * 4 + 0 < PITCH) *(u32x2_a8*)(o + 0) = u32x2_a8{x0, x1};
+            if (NF * 4 + 2 < PITCH) *(u32x2_a8*)(o + 2) = u32x2_a8{x2, x3};
+        }
+}
+
 template <bool SUB, int PITCH>
 __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __restrict__ src_base, const uint8_t* __restrict__ ref_base,
                                                               const SvtHipMeSearchDesc* __restrict__ descs, const uint32_t n, const int win_dw,
@@ -379,7 +475,9 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
         }
     }
     const int width = 64 + W - 1;
-    stage_rows_wide_cpr<64>(win, PITCH, ref_base + d.ref_off, d.ref_stride, width, 64 + H - 1, (width + 15) >> 4, l);
+    // 64 <= width <= 87: four full 16-byte chunks per row, five from W = 17 on (never with the 18-dword pitch of the areas up to 8 wide)
+    if (PITCH >= 22 && (width >> 4) == 5) stage_window_wave<5, PITCH>(win, ref_base + d.ref_off, d.ref_stride, width, 64 + H - 1, l);
+    else stage_window_wave<4, PITCH>(win, ref_base + d.ref_off, d.ref_stride, width, 64 + H - 1, l);
     __builtin_amdgcn_wave_barrier(); // the slice belongs to this wave alone: LDS program order is enough on the hardware
 
     uint32_t best8 = 0xffffffffu, best16 = 0xffffffffu, best32 = 0xffffffffu, best64 = 0xffffffffu;
