@@ -219,7 +219,8 @@ __device__ __forceinline__ uint32_t dpp_scatter_sum_quads(const uint32_t (&v)[4]
 // pos = yl * 64 + 4 * g + x.  Inside the loops a key carries only the wave-uniform part of its position (a scalar operand); the part that is a constant of the lane
 // -- x for 16x16, x and the step within the group of four for 32x32 / 64x64 -- occupies disjoint bits and is ORed into the lane's winner once at the end.  Every key
 // a lane compares shares that part, so the order of its keys, and with it "first minimum in raster order", is unchanged.
-// 32x32 and 64x64 are evaluated once per group of four y steps (dpp_scatter_sum_quads): quad c of a row then stands for step c of the group.
+// 32x32 and 64x64 are evaluated once per group of four y steps (dpp_scatter_sum_quads): quad c of a row then stands for step c of the group; a last group of
+// one step is evaluated once per four x groups (the pool, below): quad c then stands for x group c.
 // FULL: the tile width is a multiple of 4, no strip has invalid positions.
 template <bool SUB, bool FULL, int PITCH = ME_PITCH>
 __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ win, const uint32_t (&s)[8][2], int Wt, int Ht, int g0, int gstep, int l,
@@ -235,6 +236,15 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
     // one (261 120 and 1 044 480) and still fit the 21 bits a key has for the SAD, so its key loses against the key of any step that exists.
     constexpr uint32_t NO_STEP = 0x1ffffu;
     uint32_t       b16 = 0xffffffffu, b32 = 0xffffffffu, b64 = 0xffffffffu; // winners with the lane-constant position bits still missing
+    // A last group of ONE step (Ht % 4 == 1) does not pay a reduce-scatter with three sentinels: it is pooled over up to four x groups.  Behind the y loop of an
+    // x group the step's 32x32 sum is all-reduced over the row (two adds) and kept by the lanes of quad kc only, kc = the x group's number within the pool, so
+    // that after four x groups quad c holds the remainder step of x group c and ONE pass over the 32x32 / 64x64 levels serves them all.  The lane-constant part
+    // of such a key's position is 4 * gstep * c (the x groups of a pool lie gstep apart; the pool's first group contributes none of these bits: it is a multiple
+    // of 4 where gstep = 1, and below 4 where gstep = 4 and a wave has a single pool).  A quad without an x group, and an invalid position of the last strip,
+    // keep NO_SUM: at least every real 32x32 sum and, four times, above every real 64x64 sum, within the 21 bits.
+    constexpr uint32_t NO_SUM = 0x7ffffu;
+    uint32_t       p32 = NO_SUM, b32p = 0xffffffffu, b64p = 0xffffffffu;
+    int            kc = 0;
     for (int g = g0; g < G; g += gstep) {
         const uint32_t* colp   = win + (by * 8) * PITCH + bx * 2 + g;
         const int       nvalid = (Wt - 4 * g) < 4 ? (Wt - 4 * g) : 4;
@@ -249,6 +259,7 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
             rb[r] = *(const U64A4*)(colp + r * PITCH + 1);
         }
         uint32_t pos = (uint32_t)(4 * g); // wave-uniform: the keys take it as a scalar operand
+        uint32_t v0  = 0;                 // the 16x16 SADs of the first step of the group walked last
         for (int yb = 0; yb < Ht; yb += 8) {
             const uint32_t* rowp = colp + (yb + 7) * PITCH;
 #pragma unroll
@@ -284,19 +295,37 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
                             pos += ME_TW;
                         }
                     }
-                    // 32x32 = 4 quads of a 16-lane row, 64x64 = 4 rows: once for the group; quad c now stands for step c
-                    const uint32_t gpos  = (uint32_t)(4 * g + ME_TW * (yb + 4 * h));
-                    const uint32_t sad32 = dpp_scatter_sum_quads(v);
-                    const uint32_t k32   = (sad32 << KEY_POS_BITS) | gpos;
-                    b32 = umin32(b32, FULL ? k32 : (k32 | invq));
-                    // row sums across the wave with the gfx950 row / half swaps: lane-wise, every lane of a row holds a different (step, x)
-                    const auto     x16   = __builtin_amdgcn_permlane16_swap(sad32, sad32, false, false);
-                    const uint32_t pair  = x16[0] + x16[1];
-                    const auto     x32   = __builtin_amdgcn_permlane32_swap(pair, pair, false, false);
-                    const uint32_t sad64 = x32[0] + x32[1];
-                    const uint32_t k64   = (sad64 << KEY_POS_BITS) | gpos;
-                    b64 = umin32(b64, FULL ? k64 : (k64 | invq));
+                    v0 = v[0];
+                    if (yb + 4 * h + 1 < Ht) { // (a group of one step goes into the pool, below)
+                        // 32x32 = 4 quads of a 16-lane row, 64x64 = 4 rows: once for the group; quad c now stands for step c
+                        const uint32_t gpos  = (uint32_t)(4 * g + ME_TW * (yb + 4 * h));
+                        const uint32_t sad32 = dpp_scatter_sum_quads(v);
+                        const uint32_t k32   = (sad32 << KEY_POS_BITS) | gpos;
+                        b32 = umin32(b32, FULL ? k32 : (k32 | invq));
+                        // row sums across the wave with the gfx950 row / half swaps: lane-wise, every lane of a row holds a different (step, x)
+                        const auto     x16   = __builtin_amdgcn_permlane16_swap(sad32, sad32, false, false);
+                        const uint32_t pair  = x16[0] + x16[1];
+                        const auto     x32   = __builtin_amdgcn_permlane32_swap(pair, pair, false, false);
+                        const uint32_t sad64 = x32[0] + x32[1];
+                        const uint32_t k64   = (sad64 << KEY_POS_BITS) | gpos;
+                        b64 = umin32(b64, FULL ? k64 : (k64 | invq));
+                    }
                 }
+            }
+        }
+        if ((Ht & 3) == 1) { // v0 is the remainder step: its 32x32 sum, all-reduced over the quads of a row, kept by quad kc
+            const uint32_t sum = dpp_add_row_ror4(dpp_add_row_ror8(v0));
+            if (c == kc && (FULL || q < nvalid)) p32 = sum;
+            if (++kc == 4 || g + gstep >= G) { // the pool is full, or this was the last x group: quad c stands for x group g - (kc - 1 - c) * gstep
+                const uint32_t gpos  = (uint32_t)(4 * (g - (kc - 1) * gstep) + ME_TW * (Ht - 1));
+                b32p = umin32(b32p, (p32 << KEY_POS_BITS) | gpos);
+                const auto     x16   = __builtin_amdgcn_permlane16_swap(p32, p32, false, false);
+                const uint32_t pair  = x16[0] + x16[1];
+                const auto     x32   = __builtin_amdgcn_permlane32_swap(pair, pair, false, false);
+                const uint32_t sad64 = x32[0] + x32[1];
+                b64p = umin32(b64p, (sad64 << KEY_POS_BITS) | gpos);
+                p32 = NO_SUM;
+                kc  = 0;
             }
         }
     }
@@ -305,6 +334,9 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
     best16 = umin32(best16, b16 | (uint32_t)q);
     best32 = umin32(best32, b32 | (uint32_t)(q | (c << 6)));
     best64 = umin32(best64, b64 | (uint32_t)(q | (c << 6)));
+    // the pooled remainder steps: x = q, x group within the pool = c (all ones where there was no pool)
+    best32 = umin32(best32, b32p | (uint32_t)(q | (4 * gstep * c)));
+    best64 = umin32(best64, b64p | (uint32_t)(q | (4 * gstep * c)));
 }
 
 template <bool SUB>
@@ -487,8 +519,12 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
     best16 = dpp_min_quad_xor2(dpp_min_quad_xor1(best16));
     best32 = dpp_min_row_ror8(dpp_min_row_ror4(dpp_min_quad_xor2(dpp_min_quad_xor1(best32))));
     best64 = dpp_min_row_ror8(dpp_min_row_ror4(dpp_min_quad_xor2(dpp_min_quad_xor1(best64))));
-    best64 = umin32(best64, (uint32_t)__shfl_xor((int)best64, 16));
-    best64 = umin32(best64, (uint32_t)__shfl_xor((int)best64, 32));
+    { // every lane of a row holds the row's minimum: the row / half swaps pair the rows lane-wise
+        const auto x16 = __builtin_amdgcn_permlane16_swap(best64, best64, false, false);
+        best64         = umin32(x16[0], x16[1]);
+        const auto x32 = __builtin_amdgcn_permlane32_swap(best64, best64, false, false);
+        best64         = umin32(x32[0], x32[1]);
+    }
     const int xo = d.x_search_area_origin, yo = d.y_search_area_origin;
     auto emit = [&](const int idx, const uint32_t key, const bool is8) {
         const uint32_t sad = is8 ? (key >> 16) : (key >> KEY_POS_BITS);
@@ -497,9 +533,14 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
         best_mv[o + idx]  = ((uint32_t)(uint16_t)(Y + yo) << 16) | (uint16_t)(X + xo);
     };
     emit(21 + l, best8, true);
-    if ((l & 3) == 0) emit(5 + (l >> 2), best16, false);
-    if ((l & 15) == 0) emit(1 + (l >> 4), best32, false);
-    if (l == 0) emit(0, best64, false);
+    // The 21 large blocks in one pass: lane j < 21 stores output j.  After the all-reduces above every lane of a quad holds its 16x16 winner, every lane of a row its
+    // 32x32 winner and every lane the 64x64 one, so lane 1 of each quad offers the first, lane 2 the second, lanes 0 and 3 the third, and a single cross-lane read fetches them all:
+    // output 0 is lane 0's own, outputs 1-4 come from lane 2 of row j - 1, outputs 5-20 from lane 1 of quad j - 5 (ds_bpermute takes the lane as a byte address).
+    const int      q    = l & 3;
+    const uint32_t mine = q == 1 ? best16 : (q == 2 ? best32 : best64);
+    const int      r32  = 64 * l - 56, r16 = 16 * l - 76;
+    const uint32_t key  = (uint32_t)__builtin_amdgcn_ds_bpermute(l < 5 ? (r32 > 0 ? r32 : 0) : r16, (int)mine);
+    if (l < 21) emit(l, key, false);
 }
 
 __global__ void me_finalize_kernel(const SvtHipMeSearchDesc* __restrict__ descs, uint32_t n, const unsigned long long* __restrict__ keys,

@@ -11,12 +11,18 @@ Compiles sad.hip for gfx950 with the flags of csrc/Makefile plus `-S --cuda-devi
   search instance  : one per instantiation of me_search_strips (FULL = W % 4 == 0, and the general one); an instance starts at a ring prologue.
                        prologue : per x group, the blocks without a v_qsad_pk_u16_u8 or a v_permlane32_swap
                        step     : a block with 16 (sub_sad: 8) qsad = one y step; its tail = VALU - qsad
-                       group    : a block with v_permlane32_swap = the 32x32 / 64x64 levels of a group of four steps
-  final            : after the last search block: DPP minima over the lanes and the stores.
+                       group    : a block with v_permlane32_swap and the bank-masked adds of the reduce-scatter = the 32x32 / 64x64 levels of a group
+                                  of two to four steps
+                       pool add : a block with full-row v_add_u32_dpp row_ror and neither qsad nor swap = a last group of ONE step (H % 4 == 1): its 32x32
+                                  sum goes into the pool of up to four x groups
+                       pool     : a block with v_permlane32_swap and no reduce-scatter = the 32x32 / 64x64 levels of a pool, once per four x groups
+  final            : from the first v_min_u32_dpp on: minima over the lanes, the cross-lane read (ds_bpermute, counted apart: LDS pipe) and the two store
+                     passes.  The stores of an empty search area (the loop at the very end) are laid out here too; no wave with an area runs them.
 
 Static counts are exact.  "Executed" weights them with the trip counts of the area: G = ceil(W / 4) x groups, H steps and ceil(H / 4) groups each.  The unrolled
 ring has eight step variants that differ by a few scalar-fed instructions, and which of them a given H runs is not derived here: the step and group terms use the
 mean over the variants, and the [min, max] over the variants is printed as the bound.  Predicated blocks (skipped when no lane needs them) count as executed.
+Groups per x group: H // 4 full ones, one more (with the sentinel) for H % 4 in {2, 3}; H % 4 == 1 is a pool add per x group and ceil(G / 4) pools per wave.
 SQ_INSTS_VALU / SQ_WAVES of a counter pass on the GPU is the exact figure; this script is the desk check before that pass.
 """
 import argparse
@@ -45,29 +51,36 @@ def compile_asm(out):
 def blocks_of(lines, name):
     start = next(i for i, l in enumerate(lines) if re.match(r"^_Z\w*%s\w*:" % re.escape(name), l))
     end = next(i for i in range(start, len(lines)) if lines[i].strip().startswith("s_endpgm"))
-    out, cur = [], {"label": "entry", "ops": [], "to": []}
+    out, cur = [], {"label": "entry", "ops": [], "txt": [], "to": []}
     for l in lines[start + 1:end + 1]:
         t = l.split(";")[0].strip()
         m = re.match(r"^(\.LBB\w+):", t)
         if m:
             out.append(cur)
-            cur = {"label": m.group(1), "ops": [], "to": []}
+            cur = {"label": m.group(1), "ops": [], "txt": [], "to": []}
             continue
         if not t or t.startswith("."):
             continue
         op = t.split()[0]
         cur["ops"].append(op)
+        cur["txt"].append(t)
         if op.startswith("s_cbranch") or op == "s_branch":
             cur["to"].append(t.split()[1])
             out.append(cur)
-            cur = {"label": cur["label"] + "+", "ops": [], "to": []}
+            cur = {"label": cur["label"] + "+", "ops": [], "txt": [], "to": []}
     out.append(cur)
     out = [b for b in out if b["ops"]]
     for b in out:
         b["valu"] = sum(o.startswith("v_") for o in b["ops"])
         b["qsad"] = sum(o.startswith("v_qsad_pk_u16_u8") for o in b["ops"])
         b["dsr"] = sum(o.startswith("ds_read") for o in b["ops"])
-        b["grp"] = any(o.startswith("v_permlane32_swap") for o in b["ops"])
+        swap = any(o.startswith("v_permlane32_swap") for o in b["ops"])
+        scatter = any(t.startswith("v_add_u32_dpp") and "bank_mask:0x3" in t for t in b["txt"])
+        b["grp"] = swap and scatter
+        b["pool"] = swap and not scatter
+        b["padd"] = not swap and not b["qsad"] and any(t.startswith("v_add_u32_dpp") and "row_ror" in t and "bank_mask:0xf" in t for t in b["txt"])
+        b["fin"] = any(o.startswith("v_min_u32_dpp") for o in b["ops"])
+        b["bperm"] = sum(o.startswith("ds_bpermute") for o in b["ops"])
     return out
 
 
@@ -96,7 +109,8 @@ def main():
     md = metadata(lines, a.kernel)
     idx = {b["label"]: i for i, b in enumerate(bl)}
     starts = [i for i, b in enumerate(bl) if b["dsr"] >= 14 and not b["qsad"]]  # ring prologues
-    last_search = max(i for i, b in enumerate(bl) if b["qsad"] or b["grp"])
+    fins = [i for i, b in enumerate(bl) if b["fin"]]
+    last_search = (fins[0] - 1) if fins else max(i for i, b in enumerate(bl) if b["qsad"] or b["grp"])
     print("kernel %s: VGPR %d, SGPR %d, scratch %d bytes, spilled VGPRs %d" % (a.kernel, md["vgpr"], md["sgpr"], md["scratch"], md["spill_vgpr"]))
     print("static: VALU %d, of them qsad %d, in %d basic blocks" % (sum(b["valu"] for b in bl), sum(b["qsad"] for b in bl), len(bl)))
 
@@ -124,26 +138,38 @@ def main():
           (st_static, W, H, st_exec, trips, chunks))
 
     G, groups = (W + 3) // 4, (H + 3) // 4
+    pooled = any(b["padd"] for b in bl)
+    if pooled and H % 4 == 1:
+        groups -= 1
+    n_padd, n_pool = (1, -(-G // 4)) if pooled and H % 4 == 1 else (0, 0)
     total = {}
     for k, s0 in enumerate(starts):
         s1 = starts[k + 1] if k + 1 < len(starts) else last_search + 1
         inst = bl[s0:s1]
         steps = [b for b in inst if b["qsad"]]
         grp = [b for b in inst if b["grp"] and not b["qsad"]]
-        other = [b for b in inst if not b["qsad"] and not b["grp"]]
+        padd = [b["valu"] for b in inst if b["padd"]] or [0]
+        pool = [b["valu"] for b in inst if b["pool"]] or [0]
+        other = [b for b in inst if not b["qsad"] and not b["grp"] and not b["padd"] and not b["pool"]]
         tails = [b["valu"] - b["qsad"] for b in steps]
         gt = [b["valu"] for b in grp] or [0]  # (no group blocks: the levels are part of every step)
         q = steps[0]["qsad"]
         mean = lambda v: sum(v) / len(v)  # noqa: E731
         pro = sum(b["valu"] for b in other)
-        ex = [G * (pro + H * (q + f(tails)) + groups * f(gt)) for f in (min, mean, max)]
+        ex = [G * (pro + H * (q + f(tails)) + groups * f(gt) + n_padd * f(padd)) + n_pool * f(pool) for f in (min, mean, max)]
         total[k] = (sum(tails), ex)
         print("search instance %d : %d step blocks, tail VALU per step %s (mean %.1f) + %d qsad; %d group blocks, VALU per group of four steps %s (mean %.1f); "
               "prologue and loop control %d per x group" % (k, len(steps), sorted(tails), mean(tails), q, len(grp), sorted(gt), mean(gt), pro))
-        print("                    executed at %dx%d: %d x groups x (%d + %d steps x (%d + tail) + %d groups x group) = %.0f  [%d, %d]" %
-              (W, H, G, pro, H, q, groups, ex[1], ex[0], ex[2]))
-    fin = sum(b["valu"] for b in bl[last_search + 1:])
-    print("final minima + emit : %d" % fin)
+        if pooled:
+            print("                    pool add (a last group of one step) %s per x group, pool %s per four x groups" % (sorted(padd), sorted(pool)))
+        print("                    executed at %dx%d: %d x groups x (%d + %d steps x (%d + tail) + %d groups x group + %d x pool add) + %d x pool = %.0f  [%d, %d]" %
+              (W, H, G, pro, H, q, groups, n_padd, n_pool, ex[1], ex[0], ex[2]))
+    final = bl[last_search + 1:]
+    back = [idx[t] - (last_search + 1) for i, b in enumerate(final) for t in b["to"] if t in idx and last_search + 1 <= idx[t] <= last_search + 1 + i]
+    empty = final[max(min(back) - 1, 0):] if back else []  # the store loop of an empty area and its preheader
+    fin = sum(b["valu"] for b in final) - sum(b["valu"] for b in empty)
+    print("final minima + emit : %d, ds_bpermute %d (and %d in the stores of an empty area, which no wave with an area runs)" %
+          (fin, sum(b["bperm"] for b in final), sum(b["valu"] for b in empty)))
     full = min(total, key=lambda k: total[k][0])  # the instantiation without the invalid-position ORs
     which = full if W % 4 == 0 else max(total, key=lambda k: total[k][0])
     ex = total[which][1]
