@@ -810,6 +810,63 @@ void svt_hip_txfm_quant_roundtrip_batch(const int16_t *residual_base, const void
                                         int tx_size, int bd, int quant_mode, const SvtHipQuantParams *qparams, const int16_t *iscan_tables,
                                         const uint8_t *qm_tables, const uint8_t *iqm_tables, int32_t *qcoeff, int32_t *dqcoeff, uint16_t *eob, void *stream);
 
+/* ------------------------------------------- RD distortion: SSE, coefficient SSE, psy-rd energy (last arrow) --------- */
+/* One launch, n blocks of mixed sizes on resident planes.  Offsets and strides in pixels (8-bit planes: is16 = 0; uint16_t planes: is16 = 1). */
+typedef struct SvtHipDistDesc {
+    uint64_t in_off, rec_off;
+    uint32_t in_stride, rec_stride;
+    uint16_t width, height;
+    uint32_t reserved;
+} SvtHipDistDesc;
+#define SVT_HIP_DIST_SSE 1
+#define SVT_HIP_DIST_PSY 2
+/* what = SVT_HIP_DIST_SSE | SVT_HIP_DIST_PSY (both come from the same loaded pixels; an array that is not asked for is not touched).
+ * sse_out[i] -> svt_spatial_full_distortion_kernel_c (picture_operators_c.c:65-83) / svt_full_distortion_kernel16_bits_c (pic_operators.c:174-197), any width and
+ *               height >= 1.
+ * psy_out[i] -> the RAW value of svt_psy_distortion / svt_psy_distortion_hbd (psy_rd.c:135-166, :241-271), before the psy_rd factor; the reference's precondition
+ *               holds: width and height multiples of 4, of 8 when both are >= 8 (8x8 sub-blocks then, 4x4 otherwise). */
+void svt_hip_pixel_dist_batch(const void *input_base, const void *recon_base, const SvtHipDistDesc *descs, uint32_t n, int is16, int what,
+                              uint64_t *sse_out, uint64_t *psy_out, void *stream);
+typedef struct SvtHipCoeffDistDesc {
+    uint64_t coeff_off, recon_off;       /* int32 elements from coeff_base / recon_coeff_base */
+    uint32_t coeff_stride, recon_stride;
+    uint16_t width, height;
+    uint8_t  cbf_zero;                   /* 1: svt_full_distortion_kernel_cbf_zero32_bits -- recon_coeff is not read, both results are sum c^2 */
+    uint8_t  pad[3];
+} SvtHipCoeffDistDesc;
+/* dist_out[i][0] = DIST_CALC_RESIDUAL = sum (coeff - recon_coeff)^2, dist_out[i][1] = DIST_CALC_PREDICTION = sum coeff^2, 64-bit
+ * (svt_full_distortion_kernel32_bits_c / svt_full_distortion_kernel_cbf_zero32_bits_c, pic_operators.c:150-221). */
+void svt_hip_coeff_dist_batch(const int32_t *coeff_base, const int32_t *recon_coeff_base, const SvtHipCoeffDistDesc *descs, uint32_t n,
+                              uint64_t *dist_out /* [n][2] */, void *stream);
+/* The round trip that returns what it cost: svt_hip_txfm_quant_roundtrip_batch, then svt_hip_coeff_dist_batch on (forward coefficients after the svt_handle_transform
+ * repack, dequantised coefficients) over min(W,32) x min(H,32) at stride min(W,32) with cbf_zero where eob == 0, then svt_hip_pixel_dist_batch(src, pred) and
+ * (src, recon) over W x H -- bit-identical to that composition.  The coefficient sums leave the round-trip kernel itself (dqcoeff may be NULL); the pixel terms are a
+ * second launch on the same stream.  psy_* are raw (before the psy_rd factor). */
+typedef struct SvtHipPlaneRef { uint64_t off; uint32_t stride, reserved; } SvtHipPlaneRef; /* pixels from src_base */
+typedef struct SvtHipRdDist { uint64_t coeff_dist[2], sse_pred, sse_recon, psy_pred, psy_recon; } SvtHipRdDist;
+void svt_hip_txfm_quant_roundtrip_dist_batch(const int16_t *residual_base, const void *pred_base, void *recon_base, const SvtHipRoundtripDesc *descs, uint32_t n,
+                                             int tx_size, int bd, int quant_mode, const SvtHipQuantParams *qparams, const int16_t *iscan_tables,
+                                             const uint8_t *qm_tables, const uint8_t *iqm_tables, int32_t *qcoeff, int32_t *dqcoeff, uint16_t *eob,
+                                             const void *src_base, const SvtHipPlaneRef *src, SvtHipRdDist *out, void *stream);
+/* single-call forms with the reference's prototypes: the four dispatch pointers of common_dsp_rtcd.h:160, :161, :167, :169 (exported, NOT installed by
+ * svt_hip_setup_rtcd: INTEGRATION.md), svt_spatial_psy_distortion_kernel_c (common_dsp_rtcd.h:165; the psy term only when psy_rd > 0) and psy_rd.h:23-32
+ * (svt_get_psy_full_dist_hip = get_svt_psy_full_dist: (uint64_t)(raw * psy_rd) in IEEE double on the host, psy_rd.c:292). */
+uint64_t svt_spatial_full_distortion_kernel_hip(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset,
+                                                uint32_t recon_stride, uint32_t area_width, uint32_t area_height);
+uint64_t svt_full_distortion_kernel16_bits_hip(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset,
+                                               uint32_t recon_stride, uint32_t area_width, uint32_t area_height);
+void     svt_full_distortion_kernel32_bits_hip(int32_t *coeff, uint32_t coeff_stride, int32_t *recon_coeff, uint32_t recon_coeff_stride,
+                                               uint64_t distortion_result[2], uint32_t area_width, uint32_t area_height);
+void     svt_full_distortion_kernel_cbf_zero32_bits_hip(int32_t *coeff, uint32_t coeff_stride, uint64_t distortion_result[2], uint32_t area_width,
+                                                        uint32_t area_height);
+uint64_t svt_spatial_psy_distortion_kernel_hip(uint8_t *input, uint32_t input_offset, uint32_t input_stride, uint8_t *recon, int32_t recon_offset,
+                                               uint32_t recon_stride, uint32_t area_width, uint32_t area_height, double psy_rd);
+uint64_t svt_psy_distortion_hip(const uint8_t *input, uint32_t input_stride, const uint8_t *recon, uint32_t recon_stride, uint32_t width, uint32_t height);
+uint64_t svt_psy_distortion_hbd_hip(const uint16_t *input, uint32_t input_stride, const uint16_t *recon, uint32_t recon_stride, uint32_t width,
+                                    uint32_t height);
+uint64_t svt_get_psy_full_dist_hip(const void *s, uint32_t so, uint32_t sp, const void *r, uint32_t ro, uint32_t rp, uint32_t w, uint32_t h, uint8_t is_hbd,
+                                   double psy_rd);
+
 /* ------------------------------------------- picture preparation for ME ------------------------- */
 /* downsample_2d -> svt_aom_downsample_2d_c (aom_dsp_rtcd.h:841, pic_analysis_process.c:130-160): out(x, y) = (2x2 box at the centre of cell
  * (x, y) of decim_step x decim_step input pixels + 2) >> 2; host pointers (RTCD form). */

@@ -238,6 +238,30 @@ for _n in ("64x64", "32x64", "64x32", "16x64", "64x16"):
     PROTOTYPES["svt_handle_transform%s_N2_N4_hip" % _n] = (C.c_uint64, [vp])
 
 
+# RD distortion (csrc/dist.hip): SvtHipDistDesc, SvtHipCoeffDistDesc, SvtHipPlaneRef, SvtHipRdDist
+DIST_SSE, DIST_PSY = 1, 2
+DistDesc = np.dtype([("in_off", "<u8"), ("rec_off", "<u8"), ("in_stride", "<u4"), ("rec_stride", "<u4"), ("width", "<u2"), ("height", "<u2"), ("reserved", "<u4")])
+CoeffDistDesc = np.dtype([("coeff_off", "<u8"), ("recon_off", "<u8"), ("coeff_stride", "<u4"), ("recon_stride", "<u4"), ("width", "<u2"), ("height", "<u2"),
+                          ("cbf_zero", "u1"), ("pad", "u1", (3,))])
+PlaneRef = np.dtype([("off", "<u8"), ("stride", "<u4"), ("reserved", "<u4")])
+RdDist = np.dtype([("coeff_dist", "<u8", (2,)), ("sse_pred", "<u8"), ("sse_recon", "<u8"), ("psy_pred", "<u8"), ("psy_recon", "<u8")])
+assert DistDesc.itemsize == 32 and CoeffDistDesc.itemsize == 32 and PlaneRef.itemsize == 16 and RdDist.itemsize == 48
+_SD = [vp, C.c_uint32, C.c_uint32, vp, C.c_int32, C.c_uint32, C.c_uint32, C.c_uint32]
+PROTOTYPES.update({
+    "svt_hip_pixel_dist_batch": (None, [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]),
+    "svt_hip_coeff_dist_batch": (None, [vp, vp, vp, C.c_uint32, vp, vp]),
+    "svt_hip_txfm_quant_roundtrip_dist_batch": (None, [vp, vp, vp, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "svt_spatial_full_distortion_kernel_hip": (C.c_uint64, _SD),
+    "svt_full_distortion_kernel16_bits_hip": (C.c_uint64, _SD),
+    "svt_full_distortion_kernel32_bits_hip": (None, [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]),
+    "svt_full_distortion_kernel_cbf_zero32_bits_hip": (None, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32]),
+    "svt_spatial_psy_distortion_kernel_hip": (C.c_uint64, _SD + [C.c_double]),
+    "svt_psy_distortion_hip": (C.c_uint64, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "svt_psy_distortion_hbd_hip": (C.c_uint64, [vp, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "svt_get_psy_full_dist_hip": (C.c_uint64, [vp, C.c_uint32, C.c_uint32, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint8, C.c_double]),
+})
+
+
 LpfEdge = np.dtype([("x", "<u4"), ("y", "<u4"), ("vertical", "u1"), ("length", "u1"), ("blimit", "u1"), ("limit", "u1"), ("thresh", "u1"), ("pad", "u1", (3,))])
 assert LpfEdge.itemsize == 16
 for _len in (4, 6, 8, 14):

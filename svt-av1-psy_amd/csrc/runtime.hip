@@ -10,6 +10,7 @@ namespace svthip { // (one per kernel file: SVT_HIP_DEFINE_WARM)
 void warm_cdef(hipStream_t st);
 void warm_cdef_pick(hipStream_t st);
 void warm_deblock(hipStream_t st);
+void warm_dist(hipStream_t st);
 void warm_hme(hipStream_t st);
 void warm_lr_search(hipStream_t st);
 void warm_lr_stats(hipStream_t st);
@@ -839,6 +840,7 @@ static void warmup_impl(int stage_arenas, size_t first_arena_bytes) {
     svthip::warm_cdef(c.stream);
     svthip::warm_cdef_pick(c.stream);
     svthip::warm_deblock(c.stream);
+    svthip::warm_dist(c.stream);
     svthip::warm_hme(c.stream);
     svthip::warm_lr_search(c.stream);
     svthip::warm_lr_stats(c.stream);

@@ -87,6 +87,9 @@ struct SvtHipTplSrcParams;
 struct SvtHipTplReconParams;
 struct SvtHipTplSrcStats;
 struct SvtHipTplReconStats;
+struct SvtHipPlaneRef;
+struct SvtHipRdDist;
+struct SvtHipRoundtripDesc;
 
 namespace svthip {
 
@@ -161,6 +164,9 @@ void tpl_full_src_launch(const ::SvtHipTplSrcParams& P, const uint8_t* src, cons
                          ::SvtHipTplSrcStats* stats, hipStream_t st);
 void tpl_full_recon_launch(const ::SvtHipTplReconParams& R, const uint8_t* src, const uint8_t* ref, const ::SvtHipTplSrcStats* ss, uint8_t* rec,
                            ::SvtHipTplReconStats* out, uint32_t* sync, int cols16, int rows16, int wt, hipStream_t st);
+// the pixel terms of svt_hip_txfm_quant_roundtrip_dist_batch (dist.hip): sse / psy of (source, prediction) and (source, reconstruction) for n blocks of w x h
+void rt_pixel_dist_launch(const void* src_base, const ::SvtHipPlaneRef* src, const void* pred_base, const void* recon_base, const ::SvtHipRoundtripDesc* descs, uint32_t n,
+                          int w, int h, int is16, ::SvtHipRdDist* out, hipStream_t st);
 // device-resident copies of host picture planes kept across host calls (runtime.hip): acquire pins an entry for (host buffer, content id) on the current device
 uint8_t* plane_cache_acquire(const void* host_ptr, uint64_t id, size_t bytes, bool* hit, int* token);
 void     plane_cache_release(int token, bool now_ready);

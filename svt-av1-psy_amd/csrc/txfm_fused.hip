@@ -14,12 +14,15 @@
 
 namespace {
 
-template <typename PIX, int W, int H>
+// DIST: the block's coefficient-domain distortion (svt_full_distortion_kernel32_bits / _cbf_zero32_bits, pic_operators.c:150-221) leaves the kernel too, summed while the
+// forward and the dequantised coefficients are both at hand in the quantizer loop -- svt_hip_txfm_quant_roundtrip_dist_batch.  DIST = false is the kernel as it always was.
+template <typename PIX, int W, int H, bool DIST = false>
 __global__ __launch_bounds__(256) void txfm_roundtrip_kernel(const int16_t* __restrict__ res_base, const PIX* __restrict__ pred_base, PIX* __restrict__ recon_base,
                                                              const SvtHipRoundtripDesc* __restrict__ descs, const uint32_t n, const int bd, const int qmode,
                                                              const SvtHipQuantParams* __restrict__ qparams, const int16_t* __restrict__ iscan_tables,
                                                              const uint8_t* __restrict__ qm_tables, const uint8_t* __restrict__ iqm_tables,
-                                                             int32_t* __restrict__ qcoeff, int32_t* __restrict__ dqcoeff, uint16_t* __restrict__ eob_out) {
+                                                             int32_t* __restrict__ qcoeff, int32_t* __restrict__ dqcoeff, uint16_t* __restrict__ eob_out,
+                                                             SvtHipRdDist* __restrict__ dist_out) {
     constexpr int T = W > H ? W : H, BPW = 256 / T, PITCH = W + 1;
     constexpr int IW = W > 32 ? 32 : W, IH = H > 32 ? 32 : H, NCOEF = IW * IH; // what svt_handle_transform keeps of a 64-point block (transforms.c:2374-2542)
     constexpr int FS0 = fwd_shift0(W, H), FS1 = -fwd_shift1(W, H), FS2 = -fwd_shift2(W, H);
@@ -63,6 +66,7 @@ __global__ __launch_bounds__(256) void txfm_roundtrip_kernel(const int16_t* __re
     __syncthreads();
     // ---- quantize / dequantize the kept IW x IH corner in place (full_loop.c:29-453); position rc = row * IW + column of the packed block
     uint32_t eob = 0;
+    uint64_t d_res = 0, d_pred = 0; // DIST: sum (c - dq)^2, sum c^2 over this lane's coefficients
     if (active) {
         const SvtHipQuantParams P   = qparams[d.qparam_idx];
         const int16_t*          isc = iscan_tables + (size_t)d.iscan_idx * NCOEF;
@@ -81,6 +85,11 @@ __global__ __launch_bounds__(256) void txfm_roundtrip_kernel(const int16_t* __re
             qcoeff[base + rc] = o.q;
             if (dqcoeff) dqcoeff[base + rc] = o.dq;
             buf[r * PITCH + c] = o.dq;
+            if constexpr (DIST) {
+                const uint64_t df = (uint64_t)((int64_t)co - (int64_t)o.dq);
+                d_res += df * df;
+                d_pred += (uint64_t)((int64_t)co * (int64_t)co);
+            }
             if (o.q != 0) {
                 const uint32_t e = (uint32_t)isc[rc] + 1u;
                 eob              = e > eob ? e : eob;
@@ -93,6 +102,19 @@ __global__ __launch_bounds__(256) void txfm_roundtrip_kernel(const int16_t* __re
         eob              = o > eob ? o : eob;
     }
     if (active && t == 0) eob_out[blk] = (uint16_t)eob;
+    if constexpr (DIST) {
+#pragma unroll
+        for (int m = T >> 1; m >= 1; m >>= 1) {
+            const uint32_t rl = (uint32_t)__shfl_xor((int)(uint32_t)d_res, m), rh = (uint32_t)__shfl_xor((int)(uint32_t)(d_res >> 32), m);
+            const uint32_t pl = (uint32_t)__shfl_xor((int)(uint32_t)d_pred, m), ph = (uint32_t)__shfl_xor((int)(uint32_t)(d_pred >> 32), m);
+            d_res += ((uint64_t)rh << 32) | rl;
+            d_pred += ((uint64_t)ph << 32) | pl;
+        }
+        if (active && t == 0) { // eob == 0 is the reference's cbf_zero form: both entries are the prediction distortion
+            dist_out[blk].coeff_dist[0] = eob ? d_res : d_pred;
+            dist_out[blk].coeff_dist[1] = d_pred;
+        }
+    }
     __syncthreads();
     // ---- inverse + reconstruction (inv_txfm2d_add_c, inv_transforms.c:2459-2535) from the dequantised corner
     const int32_t rhi = (1 << (bd + 7)) - 1, rlo = -(1 << (bd + 7));
@@ -134,11 +156,15 @@ __global__ __launch_bounds__(256) void txfm_roundtrip_kernel(const int16_t* __re
 
 template <typename PIX, int W, int H>
 void launch_rt(const int16_t* res, const PIX* pred, PIX* recon, const SvtHipRoundtripDesc* descs, uint32_t n, int bd, int qmode, const SvtHipQuantParams* qp,
-               const int16_t* iscan, const uint8_t* qm, const uint8_t* iqm, int32_t* q, int32_t* dq, uint16_t* eob, hipStream_t st) {
+               const int16_t* iscan, const uint8_t* qm, const uint8_t* iqm, int32_t* q, int32_t* dq, uint16_t* eob, hipStream_t st, SvtHipRdDist* dist = nullptr) {
     constexpr int T = W > H ? W : H, BPW = 256 / T;
     const size_t  shmem = (size_t)BPW * H * (W + 1) * 4;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(txfm_roundtrip_kernel<PIX, W, H>), dim3((n + BPW - 1) / BPW), dim3(256), shmem, st, res, pred, recon, descs, n, bd, qmode, qp,
-                       iscan, qm, iqm, q, dq, eob);
+    if (dist)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(txfm_roundtrip_kernel<PIX, W, H, true>), dim3((n + BPW - 1) / BPW), dim3(256), shmem, st, res, pred, recon, descs, n, bd, qmode,
+                           qp, iscan, qm, iqm, q, dq, eob, dist);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(txfm_roundtrip_kernel<PIX, W, H, false>), dim3((n + BPW - 1) / BPW), dim3(256), shmem, st, res, pred, recon, descs, n, bd, qmode,
+                           qp, iscan, qm, iqm, q, dq, eob, (SvtHipRdDist*)nullptr);
     SVT_LAUNCH_CHECK();
 }
 #define FOR_ALL_TX_SIZES(X) \
@@ -147,31 +173,50 @@ void launch_rt(const int16_t* res, const PIX* pred, PIX* recon, const SvtHipRoun
 
 } // namespace
 
-extern "C" void svt_hip_txfm_quant_roundtrip_batch(const int16_t* residual_base, const void* pred_base, void* recon_base, const SvtHipRoundtripDesc* descs, uint32_t n,
-                                                   int tx_size, int bd, int quant_mode, const SvtHipQuantParams* qparams, const int16_t* iscan_tables,
-                                                   const uint8_t* qm_tables, const uint8_t* iqm_tables, int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob, void* stream) {
-    svthip::ensure_device();
-    if (n == 0) return;
+static void roundtrip_launch(const char* who, const int16_t* residual_base, const void* pred_base, void* recon_base, const SvtHipRoundtripDesc* descs, uint32_t n, int tx_size,
+                             int bd, int quant_mode, const SvtHipQuantParams* qparams, const int16_t* iscan_tables, const uint8_t* qm_tables, const uint8_t* iqm_tables,
+                             int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob, SvtHipRdDist* dist, hipStream_t st) {
     if (quant_mode < 0 || quant_mode > 3 || (bd > 8) != ((quant_mode & 1) != 0)) {
-        fprintf(stderr, "libsvtav1_hip: svt_hip_txfm_quant_roundtrip_batch: quant_mode %d does not match bit depth %d (0 / 2 = 8-bit, 1 / 3 = high bit depth)\n", quant_mode, bd);
+        fprintf(stderr, "libsvtav1_hip: %s: quant_mode %d does not match bit depth %d (0 / 2 = 8-bit, 1 / 3 = high bit depth)\n", who, quant_mode, bd);
         abort();
     }
-    hipStream_t st = (hipStream_t)stream;
     if (bd > 8) {
         switch (tx_size) {
-#define X(ID, W, H) case ID: launch_rt<uint16_t, W, H>(residual_base, (const uint16_t*)pred_base, (uint16_t*)recon_base, descs, n, bd, quant_mode, qparams, iscan_tables, qm_tables, iqm_tables, qcoeff, dqcoeff, eob, st); break;
+#define X(ID, W, H) case ID: launch_rt<uint16_t, W, H>(residual_base, (const uint16_t*)pred_base, (uint16_t*)recon_base, descs, n, bd, quant_mode, qparams, iscan_tables, qm_tables, iqm_tables, qcoeff, dqcoeff, eob, st, dist); break;
             FOR_ALL_TX_SIZES(X)
 #undef X
         default: fprintf(stderr, "libsvtav1_hip: bad tx_size %d\n", tx_size); abort();
         }
     } else {
         switch (tx_size) {
-#define X(ID, W, H) case ID: launch_rt<uint8_t, W, H>(residual_base, (const uint8_t*)pred_base, (uint8_t*)recon_base, descs, n, 8, quant_mode, qparams, iscan_tables, qm_tables, iqm_tables, qcoeff, dqcoeff, eob, st); break;
+#define X(ID, W, H) case ID: launch_rt<uint8_t, W, H>(residual_base, (const uint8_t*)pred_base, (uint8_t*)recon_base, descs, n, 8, quant_mode, qparams, iscan_tables, qm_tables, iqm_tables, qcoeff, dqcoeff, eob, st, dist); break;
             FOR_ALL_TX_SIZES(X)
 #undef X
         default: fprintf(stderr, "libsvtav1_hip: bad tx_size %d\n", tx_size); abort();
         }
     }
+}
+
+extern "C" void svt_hip_txfm_quant_roundtrip_batch(const int16_t* residual_base, const void* pred_base, void* recon_base, const SvtHipRoundtripDesc* descs, uint32_t n,
+                                                   int tx_size, int bd, int quant_mode, const SvtHipQuantParams* qparams, const int16_t* iscan_tables,
+                                                   const uint8_t* qm_tables, const uint8_t* iqm_tables, int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob, void* stream) {
+    svthip::ensure_device();
+    if (n == 0) return;
+    roundtrip_launch("svt_hip_txfm_quant_roundtrip_batch", residual_base, pred_base, recon_base, descs, n, tx_size, bd, quant_mode, qparams, iscan_tables, qm_tables,
+                     iqm_tables, qcoeff, dqcoeff, eob, nullptr, (hipStream_t)stream);
+}
+
+// Two launches on one stream, no host synchronisation: the round trip with the coefficient sums, then the pixel terms over the reconstruction it has just written.
+extern "C" void svt_hip_txfm_quant_roundtrip_dist_batch(const int16_t* residual_base, const void* pred_base, void* recon_base, const SvtHipRoundtripDesc* descs, uint32_t n,
+                                                        int tx_size, int bd, int quant_mode, const SvtHipQuantParams* qparams, const int16_t* iscan_tables,
+                                                        const uint8_t* qm_tables, const uint8_t* iqm_tables, int32_t* qcoeff, int32_t* dqcoeff, uint16_t* eob,
+                                                        const void* src_base, const SvtHipPlaneRef* src, SvtHipRdDist* out, void* stream) {
+    svthip::ensure_device();
+    if (n == 0) return;
+    static const uint8_t kW[19] = {4, 8, 16, 32, 64, 4, 8, 8, 16, 16, 32, 32, 64, 4, 16, 8, 32, 16, 64}, kH[19] = {4, 8, 16, 32, 64, 8, 4, 16, 8, 32, 16, 64, 32, 16, 4, 32, 8, 64, 16};
+    roundtrip_launch("svt_hip_txfm_quant_roundtrip_dist_batch", residual_base, pred_base, recon_base, descs, n, tx_size, bd, quant_mode, qparams, iscan_tables, qm_tables,
+                     iqm_tables, qcoeff, dqcoeff, eob, out, (hipStream_t)stream);
+    svthip::rt_pixel_dist_launch(src_base, src, pred_base, recon_base, descs, n, kW[tx_size], kH[tx_size], bd > 8, out, (hipStream_t)stream);
 }
 
 SVT_HIP_DEFINE_WARM(txfm_fused) // (svt_hip_warmup loads this translation unit's code object at encoder initialisation: svt_hip_common.h)
