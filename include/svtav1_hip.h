@@ -867,6 +867,45 @@ uint64_t svt_psy_distortion_hbd_hip(const uint16_t *input, uint32_t input_stride
 uint64_t svt_get_psy_full_dist_hip(const void *s, uint32_t so, uint32_t sp, const void *r, uint32_t ro, uint32_t rp, uint32_t w, uint32_t h, uint8_t is_hbd,
                                    double psy_rd);
 
+/* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
+#define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
+#define SVT_HIP_BLOCK_MEAN_PREC_SUB  1
+/* compute_block_mean_compute_variance (pic_analysis_process.c:306-1380) for every 64x64 superblock of n_pics equally shaped 8-bit luma planes, and
+ * compute_picture_spatial_statistics (:1531-1552).  Picture i starts at luma_base + i * pic_pitch; its first picture pixel is at (org_x, org_y), stride in bytes.
+ * prec = SVT_HIP_BLOCK_MEAN_PREC_SUB (what the encoder sets, enc_handle.c:4254: every other row, sum << 3, sum of squares << 11) or _FULL ((sum << 8) / 64,
+ * (sum of squares << 16) / 64).  variance = [n_pics][ceil(width / 64) * ceil(height / 64)][85] uint16_t in ME_TIER_ZERO_PU_* order (me_context.h:54-138): 64x64, 4 32x32,
+ * 16 16x16, 64 8x8, superblocks in raster order; with write_sub64 == 0 only entry 0 of each superblock is written (the reference writes the rest only when
+ * enable_adaptive_quantization == 1 || variance_octile, :1110).  pic_avg_variance = [n_pics] (may be NULL).  All pointers device; bit-exact.
+ * READABLE EXTENT: an edge superblock is read as a full 64x64 from the padded plane, as the reference reads it -- every picture must be readable over rows
+ * org_y .. org_y + 64 * ceil(height / 64) - 1 and columns org_x .. org_x + 64 * ceil(width / 64) - 1. */
+void svt_hip_picture_variance_batch(const uint8_t *luma_base, uint64_t pic_pitch, uint32_t stride, uint32_t org_x, uint32_t org_y, uint32_t width, uint32_t height,
+                                    uint32_t n_pics, int prec, int write_sub64, uint16_t *variance, uint16_t *pic_avg_variance, void *stream);
+/* svt_variance_adjust_qp + av1_get_deltaq_sb_variance_boost (rc_process.c:1403-1617) on the device table written above.  variance = [n_sb][85], qindex_in = [n_sb] what
+ * TPL left in sb_ptr->qindex, qindex_out = [n_sb] (may alias qindex_in), frame_out = one SvtHipVarBoostFrame: all four device.  strength 1-4, octile 1-8, curve 0-2,
+ * bit_depth 8 / 10 / 12.  q_fp8_table is a HOST array: q_fp8_table[i] = svt_av1_convert_qindex_to_q_fp8(i, bit_depth) for i = 0 .. 255 (rc_process.c:180-188) -- the
+ * library embeds no quantiser table, and svt_av1_compute_qdelta_fp's two searches (:190-210) run against this one.  The boost curve (double-precision pow / log2 and a
+ * truncating division, :1462-1493) is evaluated on the HOST with the C library, once per (base_q_idx, strength, curve, bit_depth, table), never on the device.
+ * Two launches on `stream`; returns 0, or -1 for an argument outside the ranges above (nothing is launched). */
+typedef struct SvtHipVarBoostFrame { int32_t normalized_base_q_idx, min_qindex, max_qindex, reserved; } SvtHipVarBoostFrame;
+int svt_hip_variance_boost_qindex(const uint16_t *variance, const uint8_t *qindex_in, uint32_t n_sb, uint8_t base_q_idx, uint8_t strength, uint8_t octile, uint8_t curve,
+                                  int bit_depth, const int32_t *q_fp8_table, uint8_t *qindex_out, SvtHipVarBoostFrame *frame_out, void *stream);
+/* The host-evaluated table itself: boost_out[v] (HOST, 65 536 entries) = what av1_get_deltaq_sb_variance_boost returns for a blended 8x8 variance v
+ * (v == 0 counts as 1, :1459).  No device call. */
+int svt_hip_variance_boost_table(uint8_t base_q_idx, uint8_t strength, uint8_t curve, int bit_depth, const int32_t *q_fp8_table, int16_t *boost_out);
+/* sub_sample_luma_generate_pixel_intensity_histogram_bins + calculate_histogram (pic_analysis_process.c:1461-1524, :166-184) on the 1/16 plane: origin = its first
+ * picture pixel.  regions_w x regions_h regions (4 x 4, or 1 along a side below 64: enc_handle.c:4248), the last of a direction takes the remainder; decim_step 1 or 4.
+ * histogram = [regions_w][regions_h][256] uint32_t ((1 + count) * 16 * decim_step^2), average_intensity_per_region = [regions_w][regions_h] uint8_t (the reference
+ * stores that byte in a uint64_t), avg_luma = one uint64_t (may be NULL).  All pointers device; bit-exact while a bin stays below 2^32. */
+void svt_hip_picture_histogram(const uint8_t *origin, uint32_t stride, uint32_t width, uint32_t height, uint32_t regions_w, uint32_t regions_h, uint32_t decim_step,
+                               uint32_t *histogram, uint8_t *average_intensity_per_region, uint64_t *avg_luma, void *stream);
+/* single-call forms with the reference's prototypes: the four dispatch pointers of aom_dsp_rtcd.c:516-519 (aom_dsp_rtcd.h:858-862; svt_compute_mean_c,
+ * svt_compute_mean_squared_values_c, svt_compute_sub_mean_8x8_c, svt_compute_interm_var_four8x8_c, pic_analysis_process.c:190-300).  Host pointers; exported, NOT
+ * installed by svt_hip_setup_rtcd. */
+uint64_t svt_compute_mean_8x8_hip(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height);
+uint64_t svt_compute_mean_square_values_8x8_hip(uint8_t *input_samples, uint32_t input_stride, uint32_t input_area_width, uint32_t input_area_height);
+uint64_t svt_compute_sub_mean_8x8_hip(uint8_t *input_samples, uint16_t input_stride);
+void     svt_compute_interm_var_four8x8_hip(uint8_t *input_samples, uint16_t input_stride, uint64_t *mean_of8x8_blocks, uint64_t *mean_of_squared8x8_blocks);
+
 /* ------------------------------------------- picture preparation for ME ------------------------- */
 /* downsample_2d -> svt_aom_downsample_2d_c (aom_dsp_rtcd.h:841, pic_analysis_process.c:130-160): out(x, y) = (2x2 box at the centre of cell
  * (x, y) of decim_step x decim_step input pixels + 2) >> 2; host pointers (RTCD form). */

@@ -262,6 +262,22 @@ PROTOTYPES.update({
 })
 
 
+# picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
+BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
+VarBoostFrame = np.dtype([("normalized_base_q_idx", "<i4"), ("min_qindex", "<i4"), ("max_qindex", "<i4"), ("reserved", "<i4")])
+assert VarBoostFrame.itemsize == 16
+PROTOTYPES.update({
+    "svt_hip_picture_variance_batch": (None, [vp, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, vp, vp, vp]),
+    "svt_hip_variance_boost_qindex": (C.c_int, [vp, vp, C.c_uint32, C.c_uint8, C.c_uint8, C.c_uint8, C.c_uint8, C.c_int, vp, vp, vp, vp]),
+    "svt_hip_variance_boost_table": (C.c_int, [C.c_uint8, C.c_uint8, C.c_uint8, C.c_int, vp, vp]),
+    "svt_hip_picture_histogram": (None, [vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
+    "svt_compute_mean_8x8_hip": (C.c_uint64, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "svt_compute_mean_square_values_8x8_hip": (C.c_uint64, [vp, C.c_uint32, C.c_uint32, C.c_uint32]),
+    "svt_compute_sub_mean_8x8_hip": (C.c_uint64, [vp, C.c_uint16]),
+    "svt_compute_interm_var_four8x8_hip": (None, [vp, C.c_uint16, vp, vp]),
+})
+
+
 LpfEdge = np.dtype([("x", "<u4"), ("y", "<u4"), ("vertical", "u1"), ("length", "u1"), ("blimit", "u1"), ("limit", "u1"), ("thresh", "u1"), ("pad", "u1", (3,))])
 assert LpfEdge.itemsize == 16
 for _len in (4, 6, 8, 14):

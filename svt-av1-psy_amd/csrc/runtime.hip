@@ -18,6 +18,7 @@ void warm_me_results(hipStream_t st);
 void warm_me_session(hipStream_t st);
 void warm_misc(hipStream_t st);
 void warm_picprep(hipStream_t st);
+void warm_picstats(hipStream_t st);
 void warm_pme(hipStream_t st);
 void warm_quant(hipStream_t st);
 void warm_restoration(hipStream_t st);
@@ -848,6 +849,7 @@ static void warmup_impl(int stage_arenas, size_t first_arena_bytes) {
     svthip::warm_me_session(c.stream);
     svthip::warm_misc(c.stream);
     svthip::warm_picprep(c.stream);
+    svthip::warm_picstats(c.stream);
     svthip::warm_pme(c.stream);
     svthip::warm_quant(c.stream);
     svthip::warm_restoration(c.stream);
