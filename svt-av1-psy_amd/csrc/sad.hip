@@ -222,12 +222,24 @@ __device__ __forceinline__ uint32_t dpp_scatter_sum_quads(const uint32_t (&v)[4]
 // 32x32 and 64x64 are evaluated once per group of four y steps (dpp_scatter_sum_quads): quad c of a row then stands for step c of the group; a last group of
 // one step is evaluated once per four x groups (the pool, below): quad c then stands for x group c.
 // FULL: the tile width is a multiple of 4, no strip has invalid positions.
-template <bool SUB, bool FULL, int PITCH = ME_PITCH>
+// QLDS (the wave kernel): the 16x16 sum of a quad is formed on the LDS pipe, which the search leaves nearly idle, instead of four DPP adds
+// and a v_perm.  `qsum` is the wave's own 16 slots of 8 bytes, one per quad: the slot is zeroed, every lane of the quad adds its four packed u16 SADs with ONE
+// 64-bit atomicAdd whose result is unused (ds_add_u64; no u16 lane can carry: 4 * 16 320 = 65 280), and lane q reads u16 number q back, zero extended.  The value
+// is consumed one step late, so that no wait for the LDS sits between a step's qsads and its tail; only the last step of a group is waited for.  This crosses
+// lanes: the LDS queue of a wave is in order on the hardware, and the fence + wave barrier keep the compiler from reordering (and order the emulator's lanes).
+constexpr int ME_WAVE_QSUM_DW = 32; // dwords of a wave's quad-sum slots, behind its window
+__device__ __forceinline__ void me_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+template <bool SUB, bool FULL, int PITCH = ME_PITCH, bool QLDS = false>
 __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ win, const uint32_t (&s)[8][2], int Wt, int Ht, int g0, int gstep, int l,
-                                                 uint32_t& best8, uint32_t& best16, uint32_t& best32, uint32_t& best64) {
+                                                 uint32_t& best8, uint32_t& best16, uint32_t& best32, uint32_t& best64, unsigned long long* qsum = nullptr) {
     const int bx = (l & 1) | ((l >> 1) & 2) | ((l >> 2) & 4);
     const int by = ((l >> 1) & 1) | ((l >> 2) & 2) | ((l >> 3) & 4);
     const int q  = l & 3, c = (l >> 2) & 3;
+    unsigned long long* const qslot = QLDS ? qsum + (l >> 2) : nullptr;               // the quad's slot
+    const uint16_t* const     qmine = QLDS ? (const uint16_t*)qslot + q : nullptr;    // position q of it
     const int      G    = (Wt + 3) >> 2;
     const uint32_t qsel = 0x0c0c0100u + 0x0202u * (uint32_t)q; // v_perm_b32 selector: u16 number q of {thi:tlo}, zero extended
     uint32_t       himask = 0xffff0000u; // in a VGPR, so that (x & himask) | pos is one v_and_or_b32 with the scalar pos (VOP3 takes no literal on gfx9)
@@ -251,6 +263,10 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
         // invalid positions (last strip when Wt % 4 != 0) are pushed to the top of the key space
         const uint32_t inv1 = nvalid > 1 ? 0u : 0xffffffffu, inv2 = nvalid > 2 ? 0u : 0xffffffffu, inv3 = nvalid > 3 ? 0u : 0xffffffffu;
         const uint32_t invq = q < nvalid ? 0u : 0xffffffffu;
+        auto track16 = [&](const uint32_t sad16, const uint32_t at) { // the 16x16 key of position q at step `at`
+            const uint32_t k16 = (sad16 << KEY_POS_BITS) | at;
+            b16 = umin32(b16, FULL ? k16 : (k16 | invq));
+        };
         // 8-row ring; each row is kept as the two overlapping 8-byte windows v_qsad_pk_u16_u8 consumes
         U64A4 ra[8], rb[8];
 #pragma unroll
@@ -285,15 +301,28 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
                             const uint32_t k0 = (lo << 16) | pos, k1 = (lo & himask) | p1, k2 = (hi << 16) | p2, k3 = (hi & himask) | p3;
                             best8 = umin32(umin32(best8, k0), k1);
                             best8 = umin32(umin32(best8, k2), k3);
-                            // 16x16 = the quad's four 8x8 (u16 lanes: 4 * 16320 < 65536, so plain adds never carry)
-                            const uint32_t tlo = dpp_add_quad_xor2(dpp_add_quad_xor1(lo));
-                            const uint32_t thi = dpp_add_quad_xor2(dpp_add_quad_xor1(hi));
-                            // lane q of the quad takes position q from here on
-                            v[j] = __builtin_amdgcn_perm(thi, tlo, qsel);
-                            const uint32_t k16 = (v[j] << KEY_POS_BITS) | pos;
-                            b16 = umin32(b16, FULL ? k16 : (k16 | invq));
+                            if (QLDS) {
+                                me_lds_order(); // (every lane has read the previous step's sum)
+                                *qslot = 0ull;
+                                me_lds_order();
+                                atomicAdd(qslot, acc);
+                                me_lds_order();
+                                v[j] = *qmine; // lane q of the quad takes position q; consumed at the next step, or behind the group
+                                if (j > 0) track16(v[j - 1], pos - ME_TW);
+                            } else {
+                                // 16x16 = the quad's four 8x8 (u16 lanes: 4 * 16320 < 65536, so plain adds never carry)
+                                const uint32_t tlo = dpp_add_quad_xor2(dpp_add_quad_xor1(lo));
+                                const uint32_t thi = dpp_add_quad_xor2(dpp_add_quad_xor1(hi));
+                                // lane q of the quad takes position q from here on
+                                v[j] = __builtin_amdgcn_perm(thi, tlo, qsel);
+                                track16(v[j], pos);
+                            }
                             pos += ME_TW;
                         }
+                    }
+                    if (QLDS) { // the group's last step: the one sum that is waited for
+                        const int left = Ht - (yb + 4 * h);
+                        track16(left >= 4 ? v[3] : (left == 3 ? v[2] : (left == 2 ? v[1] : v[0])), pos - ME_TW);
                     }
                     v0 = v[0];
                     if (yb + 4 * h + 1 < Ht) { // (a group of one step goes into the pool, below)
@@ -494,7 +523,7 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
         for (int k = l; k < SVT_HIP_ME_NUM_BLOCKS; k += 64) { best_sad[o + k] = MAX_SAD_VALUE; best_mv[o + k] = 0; }
         return;
     }
-    uint32_t* win = smem + wv * win_dw;
+    uint32_t* win = smem + wv * (win_dw + ME_WAVE_QSUM_DW); // the wave's window (win_dw is even: 8-byte aligned), and behind it its quad-sum slots
     const int bx = (l & 1) | ((l >> 1) & 2) | ((l >> 2) & 4);
     const int by = ((l >> 1) & 1) | ((l >> 2) & 2) | ((l >> 3) & 4);
     uint32_t  s[8][2];
@@ -513,8 +542,8 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
     __builtin_amdgcn_wave_barrier(); // the slice belongs to this wave alone: LDS program order is enough on the hardware
 
     uint32_t best8 = 0xffffffffu, best16 = 0xffffffffu, best32 = 0xffffffffu, best64 = 0xffffffffu;
-    if ((W & 3) == 0) me_search_strips<SUB, true, PITCH>(win, s, W, H, 0, 1, l, best8, best16, best32, best64);
-    else me_search_strips<SUB, false, PITCH>(win, s, W, H, 0, 1, l, best8, best16, best32, best64);
+    if ((W & 3) == 0) me_search_strips<SUB, true, PITCH, true>(win, s, W, H, 0, 1, l, best8, best16, best32, best64, (unsigned long long*)(win + win_dw));
+    else me_search_strips<SUB, false, PITCH, true>(win, s, W, H, 0, 1, l, best8, best16, best32, best64, (unsigned long long*)(win + win_dw));
     // lane q of a quad tracked position q of every strip: the block's winner is the smallest key of the lanes that share the block
     best16 = dpp_min_quad_xor2(dpp_min_quad_xor1(best16));
     best32 = dpp_min_row_ror8(dpp_min_row_ror4(dpp_min_quad_xor2(dpp_min_quad_xor1(best32))));
@@ -1643,7 +1672,7 @@ void svt_hip_me_fullpel_search_batch(const uint8_t* src_base, const uint8_t* ref
     if (max_w <= ME_WAVE_MAX_W && max_h <= ME_WAVE_MAX_H) { // small areas: one wave per item (see me_fullpel_wave_kernel)
         const int    G = (int)(max_w + 3) >> 2, pitch = 16 + G <= 18 ? 18 : 26; // dwords a ring load may touch: 16 + G; pitch = 2 mod 8 (bank spread of the 8 x 8 block grid)
         const int    win_dw = pitch * (64 + (int)max_h - 1);
-        const size_t shm    = (size_t)4 * win_dw * 4;
+        const size_t shm    = (size_t)4 * (win_dw + ME_WAVE_QSUM_DW) * 4; // 16x9: 4 x (7 488 + 128) = 30 464 bytes; five workgroups per CU need <= 32 768
         const dim3   grid((n + 3) / 4);
         hipStream_t  st = (hipStream_t)stream;
 #define ME_WAVE_LAUNCH(SUBV, PITCHV) hipLaunchKernelGGL(HIP_KERNEL_NAME(me_fullpel_wave_kernel<SUBV, PITCHV>), grid, dim3(256), shm, st, src_base, ref_base, descs, n, win_dw, best_sad, best_mv)

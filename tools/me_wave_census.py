@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""VALU census of me_fullpel_wave_kernel (csrc/sad.hip) from the cross-compiler's assembly: no GPU needed.
+"""VALU and LDS census of me_fullpel_wave_kernel (csrc/sad.hip) from the cross-compiler's assembly: no GPU needed.
 
   python tools/me_wave_census.py [--area 16x9] [--kernel me_fullpel_wave_kernelILb0ELi26E] [--keep x.s]
 
@@ -23,7 +23,10 @@ Static counts are exact.  "Executed" weights them with the trip counts of the ar
 ring has eight step variants that differ by a few scalar-fed instructions, and which of them a given H runs is not derived here: the step and group terms use the
 mean over the variants, and the [min, max] over the variants is printed as the bound.  Predicated blocks (skipped when no lane needs them) count as executed.
 Groups per x group: H // 4 full ones, one more (with the sentinel) for H % 4 in {2, 3}; H % 4 == 1 is a pool add per x group and ceil(G / 4) pools per wave.
-SQ_INSTS_VALU / SQ_WAVES of a counter pass on the GPU is the exact figure; this script is the desk check before that pass.
+LDS instructions (every ds_* but ds_bpermute; atomics = ds_min / ds_add, counted apart) are reported per step and, with the same weights, per wave:
+the quad sums of me_search_strips run on that pipe instead of the VALU, and four SIMDs share it.  The metadata line gives the static LDS bytes; the
+launcher's dynamic bytes per workgroup and the workgroups per CU they allow (160 KB per CU) are printed for the area.
+SQ_INSTS_VALU / SQ_WAVES and SQ_INSTS_LDS / SQ_WAVES of a counter pass on the GPU are the exact figures; this script is the desk check before that pass.
 """
 import argparse
 import os
@@ -74,6 +77,8 @@ def blocks_of(lines, name):
         b["valu"] = sum(o.startswith("v_") for o in b["ops"])
         b["qsad"] = sum(o.startswith("v_qsad_pk_u16_u8") for o in b["ops"])
         b["dsr"] = sum(o.startswith("ds_read") for o in b["ops"])
+        b["lds"] = sum(o.startswith("ds_") and not o.startswith("ds_bpermute") for o in b["ops"])
+        b["atom"] = sum(o.startswith(("ds_min", "ds_max", "ds_add", "ds_sub", "ds_or", "ds_and")) for o in b["ops"])
         swap = any(o.startswith("v_permlane32_swap") for o in b["ops"])
         scatter = any(t.startswith("v_add_u32_dpp") and "bank_mask:0x3" in t for t in b["txt"])
         b["grp"] = swap and scatter
@@ -90,7 +95,14 @@ def metadata(lines, name):
     i = text.index("- .agpr_count", 0)
     doc = [d for d in text[i:].split("  - .agpr_count") if ".name:           " + sym + "\n" in d][0]
     g = lambda k: int(re.search(r"\.%s:\s+(\d+)" % k, doc).group(1))  # noqa: E731
-    return {"vgpr": g("vgpr_count"), "sgpr": g("sgpr_count"), "scratch": g("private_segment_fixed_size"), "spill_vgpr": g("vgpr_spill_count")}
+    return {"vgpr": g("vgpr_count"), "sgpr": g("sgpr_count"), "scratch": g("private_segment_fixed_size"), "spill_vgpr": g("vgpr_spill_count"),
+            "lds_static": g("group_segment_fixed_size"), "slice_dw": slice_dw()}
+
+
+def slice_dw():
+    """Dwords a wave owns in LDS behind its window (the launcher sizes the dynamic LDS as 4 x (window + this)): the constant the source states."""
+    m = re.search(r"constexpr int ME_WAVE_QSUM_DW = (\d+);", open(os.path.join(CSRC, "sad.hip")).read())
+    return int(m.group(1)) if m else 0
 
 
 def main():
@@ -99,6 +111,7 @@ def main():
     ap.add_argument("--kernel", default="me_fullpel_wave_kernelILb0ELi26E")
     ap.add_argument("--keep", default=None, help="write the assembly here")
     ap.add_argument("--asm", default=None, help="census of an existing assembly file instead of compiling")
+    ap.add_argument("--slice-dw", type=int, default=None, help="dwords a wave owns behind its window (default: ME_WAVE_QSUM_DW of the source; 0 for a commit without it)")
     a = ap.parse_args()
     W, H = (int(v) for v in a.area.split("x"))
     path = a.asm or a.keep or os.path.join(tempfile.mkdtemp(), "sad.s")
@@ -107,6 +120,8 @@ def main():
     lines = open(path).read().split("\n")
     bl = blocks_of(lines, a.kernel)
     md = metadata(lines, a.kernel)
+    if a.slice_dw is not None:
+        md["slice_dw"] = a.slice_dw
     idx = {b["label"]: i for i, b in enumerate(bl)}
     starts = [i for i, b in enumerate(bl) if b["dsr"] >= 14 and not b["qsad"]]  # ring prologues
     fins = [i for i, b in enumerate(bl) if b["fin"]]
@@ -142,7 +157,7 @@ def main():
     if pooled and H % 4 == 1:
         groups -= 1
     n_padd, n_pool = (1, -(-G // 4)) if pooled and H % 4 == 1 else (0, 0)
-    total = {}
+    total, lds_total = {}, {}
     for k, s0 in enumerate(starts):
         s1 = starts[k + 1] if k + 1 < len(starts) else last_search + 1
         inst = bl[s0:s1]
@@ -156,6 +171,11 @@ def main():
         q = steps[0]["qsad"]
         mean = lambda v: sum(v) / len(v)  # noqa: E731
         pro = sum(b["valu"] for b in other)
+        # the same weights for the LDS pipe (means over the step / group variants)
+        lds_step, atom_step = mean([b["lds"] for b in steps]), mean([b["atom"] for b in steps])
+        lds_ex = G * (sum(b["lds"] for b in other) + H * lds_step + groups * mean([b["lds"] for b in grp] or [0])
+                      + n_padd * mean([b["lds"] for b in inst if b["padd"]] or [0])) + n_pool * mean([b["lds"] for b in inst if b["pool"]] or [0])
+        lds_total[k] = (lds_step, atom_step, lds_ex, G * H * atom_step)
         ex = [G * (pro + H * (q + f(tails)) + groups * f(gt) + n_padd * f(padd)) + n_pool * f(pool) for f in (min, mean, max)]
         total[k] = (sum(tails), ex)
         print("search instance %d : %d step blocks, tail VALU per step %s (mean %.1f) + %d qsad; %d group blocks, VALU per group of four steps %s (mean %.1f); "
@@ -175,6 +195,13 @@ def main():
     ex = total[which][1]
     print("executed VALU per wave at %dx%d (instance %d): %.0f  [%.0f, %.0f]; qsad %d" %
           (W, H, which, st_exec + ex[1] + fin, st_exec + ex[0] + fin, st_exec + ex[2] + fin, G * H * [b for b in bl if b["qsad"]][0]["qsad"]))
+    ls, at, lex, aex = lds_total[which]
+    print("LDS instructions (instance %d): %.1f per step, of them %.1f atomics; search per wave at %dx%d: %.0f, of them %.0f atomics "
+          "(+ staging: %d static in set-up, 2 stores per 16-byte chunk)" % (which, ls, at, W, H, lex, aex, sum(b["lds"] for b in pre)))
+    pitch = 18 if 16 + G <= 18 else 26
+    shm = 4 * 4 * pitch * (64 + H - 1) + 4 * 4 * md["slice_dw"]
+    print("LDS bytes per workgroup at %dx%d: 4 x (%d window + %d slice) = %d -> %d workgroups per CU (160 KB; static %d bytes)" %
+          (W, H, 4 * pitch * (64 + H - 1), 4 * md["slice_dw"], shm, min(163840 // shm, 8), md["lds_static"]))
 
 
 if __name__ == "__main__":
