@@ -867,6 +867,59 @@ uint64_t svt_psy_distortion_hbd_hip(const uint16_t *input, uint32_t input_stride
 uint64_t svt_get_psy_full_dist_hip(const void *s, uint32_t so, uint32_t sp, const void *r, uint32_t ro, uint32_t rp, uint32_t w, uint32_t h, uint8_t is_hbd,
                                    double psy_rd);
 
+/* ------------------------------------------- AV1 inter prediction: the convolve family and its compound forms (csrc/interpred.hip) --------- */
+/* One launch, n blocks of mixed sizes: the prediction svt_aom_convolve[subpel_x != 0][subpel_y != 0][compound] / svt_aom_convolveHbd[...] (inter_prediction.c:1035-1063)
+ * compute, bit for bit.  Descriptors sit at the level of those dispatch pointers: the MV clamp and the block geometry of svt_aom_inter_prediction are the caller's.
+ *   filters    av1_get_interp_filter_params_with_block_size (inter_prediction.h:137-145): the x kernel follows w, the y kernel h; a dimension <= 4 swaps REGULAR and
+ *              SHARP for sub_pel_filters_4 and SMOOTH for sub_pel_filters_4smooth.
+ *   compound 0 the `_sr` function with get_conv_params_no_round(0, 0, 0, NULL, 0, 0, bd) (convolve.h:40-64): round_0 3, round_1 11 (5 and 9 at 12 bit).
+ *   compound 1 what two calls of the `jnt_` functions leave in dst: reference 0 with do_average = 0 into a ConvBufType buffer, reference 1 with do_average = 1;
+ *   compound 2 the same with use_jnt_comp_avg = 1 and the two offsets (what svt_av1_dist_wtd_comp_weight_assign returned); round_1 = COMPOUND_ROUND1_BITS.  The
+ *              ConvBufType buffer never reaches memory.  The two references may have different phases (the case is chosen per reference).
+ * The reference's narrowings are reproduced: int16_t intermediate rows, the 8-bit 2-D function's int16_t before the last rounding (inter_prediction.c:345), the
+ * 16-bit unsigned ConvBufType of the compound paths, the 16-bit shift-and-offset of jnt_convolve_2d_copy (:650-651).
+ * READABLE EXTENT: 3 samples left of and above, 4 right of and below every w x h source block, as the reference reads; the kernel never reads outside it (a reference
+ * that is not filtered in a direction is not read beyond the block in that direction).
+ * planes.base[] are device pointers (uint8_t samples at bit_depth 8, uint16_t at 10 and 12), passed by value; dst_base and descs are device pointers.
+ * INVALID DESCRIPTORS (w or h not one of 2, 4, .. 128; a phase above 15; a filter above 3; compound above 2; a plane index >= 32 or without a base) never fault:
+ *   status == NULL  the descriptors are checked BEFORE anything is launched -- they are device memory, so a small kernel reads them and the call waits for its
+ *                   one word (one stream synchronisation per call) -- and the call returns -1 with dst untouched if any is invalid;
+ *   status != NULL  (device, n bytes) no synchronisation: the kernel writes status[i] = 0 / 1 (valid / invalid), skips the invalid blocks and the call returns 0.
+ * Returns 0, -1 (bit_depth not 8 / 10 / 12, a NULL dst_base or descs, an invalid descriptor with status == NULL) or SVT_HIP_E_DEVICE. */
+typedef struct SvtHipInterPredPlanes { const void *base[32]; } SvtHipInterPredPlanes;
+typedef struct SvtHipInterPredDesc {
+    uint64_t src_off[2];     /* samples from planes.base[plane[k]]: where the reference's `src` argument points, i.e. the block origin with the full-pel part of
+                                the (already clamped) MV applied; [1] is read only when compound != 0 */
+    uint64_t dst_off;        /* samples from dst_base */
+    uint32_t src_stride[2], dst_stride; /* samples */
+    uint8_t  plane[2];
+    uint8_t  w, h;           /* 2, 4, 8, .. 128, independently */
+    uint8_t  subpel_x[2], subpel_y[2]; /* subpel_*_q4 & SUBPEL_MASK, 0 .. 15, per reference */
+    uint8_t  filter_x, filter_y;       /* InterpFilter 0 .. 3: EIGHTTAP_REGULAR, EIGHTTAP_SMOOTH, MULTITAP_SHARP, BILINEAR */
+    uint8_t  compound;       /* 0 single reference, 1 average, 2 distance-weighted */
+    uint8_t  fwd_offset, bck_offset;   /* compound == 2 */
+    uint8_t  pad[7];
+} SvtHipInterPredDesc;
+int svt_hip_inter_pred_batch(SvtHipInterPredPlanes planes, void *dst_base, const SvtHipInterPredDesc *descs, uint32_t n, int bit_depth, uint8_t *status,
+                             void *stream);
+/* single-call forms with the reference's prototypes: the sixteen dispatch pointers of common_dsp_rtcd.h:184-215 (exported, NOT installed by svt_hip_setup_rtcd:
+ * INTEGRATION.md).  Host pointers; the eight taps are read from filter_ptr + 8 * (subpel & 15) of the caller's InterpFilterParams (taps must be 8, as in every
+ * InterpFilterParams of AV1; any values) and conv_params->round_0 / round_1 are the caller's.  The jnt_ forms honour conv_params->dst, dst_stride, do_average,
+ * use_jnt_comp_avg, fwd_offset, bck_offset as the C does: do_average == 0 writes the ConvBufType buffer and leaves dst untouched.  w, h as above (otherwise
+ * nothing is written).  ACCEPTED RANGE, outside of which a form returns having written nothing: 0 <= round_0 <= 7, round_1 >= 0, round_0 + round_1 <= 14, and
+ * round_1 <= 7 in the jnt_ forms (every value get_conv_params_no_round yields lies inside; the roundings are shift counts); bd 10 or 12 in the highbd forms.
+ * SvtHipInterpFilterParams is InterpFilterParams (definitions.h:742-747). */
+#ifdef SVT_HIP_REFERENCE_TYPES
+typedef InterpFilterParams SvtHipInterpFilterParams;
+#else
+typedef struct SvtHipInterpFilterParams {
+    const int16_t *filter_ptr;
+    uint16_t       taps, subpel_shifts;
+    uint32_t       interp_filter; /* InterpFilter, an int-sized enum */
+} SvtHipInterpFilterParams;
+#endif
+/* (the forms themselves are declared next to SvtHipConvolveParams, further down) */
+
 /* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
 #define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
 #define SVT_HIP_BLOCK_MEAN_PREC_SUB  1
@@ -1115,6 +1168,23 @@ typedef struct SvtHipConvolveParams {
     int32_t   dst_stride, round_0, round_1, plane, is_compound, use_jnt_comp_avg, fwd_offset, bck_offset, use_dist_wtd_comp_avg;
 } SvtHipConvolveParams;
 #endif
+/* the sixteen inter-prediction forms (csrc/interpred.hip; described with svt_hip_inter_pred_batch above) */
+#define SVT_HIP_DECLARE_CONVOLVE(name)                                                                                                                               \
+    void svt_av1_##name##_hip(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w, int32_t h,                                        \
+                              SvtHipInterpFilterParams *filter_params_x, SvtHipInterpFilterParams *filter_params_y, const int32_t subpel_x_q4,                       \
+                              const int32_t subpel_y_q4, SvtHipConvolveParams *conv_params);                                                                         \
+    void svt_av1_highbd_##name##_hip(const uint16_t *src, int32_t src_stride, uint16_t *dst, int32_t dst_stride, int32_t w, int32_t h,                               \
+                                     const SvtHipInterpFilterParams *filter_params_x, const SvtHipInterpFilterParams *filter_params_y,                              \
+                                     const int32_t subpel_x_q4, const int32_t subpel_y_q4, SvtHipConvolveParams *conv_params, int32_t bd);
+SVT_HIP_DECLARE_CONVOLVE(convolve_2d_copy_sr)
+SVT_HIP_DECLARE_CONVOLVE(convolve_x_sr)
+SVT_HIP_DECLARE_CONVOLVE(convolve_y_sr)
+SVT_HIP_DECLARE_CONVOLVE(convolve_2d_sr)
+SVT_HIP_DECLARE_CONVOLVE(jnt_convolve_2d_copy)
+SVT_HIP_DECLARE_CONVOLVE(jnt_convolve_x)
+SVT_HIP_DECLARE_CONVOLVE(jnt_convolve_y)
+SVT_HIP_DECLARE_CONVOLVE(jnt_convolve_2d)
+#undef SVT_HIP_DECLARE_CONVOLVE
 void svt_av1_wiener_convolve_add_src_hip(const uint8_t *src, ptrdiff_t src_stride, uint8_t *dst, ptrdiff_t dst_stride, const int16_t *filter_x,
                                          const int16_t *filter_y, int32_t w, int32_t h, const SvtHipConvolveParams *conv_params);
 void svt_av1_highbd_wiener_convolve_add_src_hip(const uint8_t *src8, ptrdiff_t src_stride, uint8_t *dst8, ptrdiff_t dst_stride,

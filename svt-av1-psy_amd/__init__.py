@@ -262,6 +262,35 @@ PROTOTYPES.update({
 })
 
 
+# AV1 inter prediction (csrc/interpred.hip): SvtHipInterPredPlanes, SvtHipInterPredDesc, SvtHipInterpFilterParams, SvtHipConvolveParams
+class InterPredPlanes(C.Structure):
+    _fields_ = [("base", vp * 32)]
+
+
+class InterpFilterParams(C.Structure):
+    """InterpFilterParams (definitions.h:742-747)."""
+    _fields_ = [("filter_ptr", vp), ("taps", C.c_uint16), ("subpel_shifts", C.c_uint16), ("interp_filter", C.c_uint32)]
+
+
+class ConvolveParams(C.Structure):
+    """ConvolveParams (definitions.h:572-585)."""
+    _fields_ = [("ref", C.c_int32), ("do_average", C.c_int32), ("dst", vp), ("dst_stride", C.c_int32), ("round_0", C.c_int32), ("round_1", C.c_int32),
+                ("plane", C.c_int32), ("is_compound", C.c_int32), ("use_jnt_comp_avg", C.c_int32), ("fwd_offset", C.c_int32), ("bck_offset", C.c_int32),
+                ("use_dist_wtd_comp_avg", C.c_int32)]
+
+
+InterPredDesc = np.dtype([("src_off", "<u8", (2,)), ("dst_off", "<u8"), ("src_stride", "<u4", (2,)), ("dst_stride", "<u4"), ("plane", "u1", (2,)), ("w", "u1"), ("h", "u1"),
+                          ("subpel_x", "u1", (2,)), ("subpel_y", "u1", (2,)), ("filter_x", "u1"), ("filter_y", "u1"), ("compound", "u1"), ("fwd_offset", "u1"),
+                          ("bck_offset", "u1"), ("pad", "u1", (7,))])
+assert InterPredDesc.itemsize == 56 and C.sizeof(InterPredPlanes) == 256 and C.sizeof(InterpFilterParams) == 16 and C.sizeof(ConvolveParams) == 56
+CONVOLVE_FORMS = ("convolve_2d_copy_sr", "convolve_x_sr", "convolve_y_sr", "convolve_2d_sr", "jnt_convolve_2d_copy", "jnt_convolve_x", "jnt_convolve_y", "jnt_convolve_2d")
+PROTOTYPES["svt_hip_inter_pred_batch"] = (C.c_int, [InterPredPlanes, vp, vp, C.c_uint32, C.c_int, vp, vp])
+_CV = [vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, vp]
+for _n in CONVOLVE_FORMS:
+    PROTOTYPES["svt_av1_%s_hip" % _n] = (None, _CV)
+    PROTOTYPES["svt_av1_highbd_%s_hip" % _n] = (None, _CV + [C.c_int32])
+
+
 # picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
 BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
 VarBoostFrame = np.dtype([("normalized_base_q_idx", "<i4"), ("min_qindex", "<i4"), ("max_qindex", "<i4"), ("reserved", "<i4")])
