@@ -920,6 +920,91 @@ typedef struct SvtHipInterpFilterParams {
 #endif
 /* (the forms themselves are declared next to SvtHipConvolveParams, further down) */
 
+/* ------------------------------------------- AV1 intra prediction: edge build, every mode, filter-intra, CfL (csrc/intrapred.hip) ---------- */
+/* One launch, n blocks of mixed sizes: what build_intra_predictors (bit_depth 8, uint8_t samples) / build_intra_predictors_high (10 / 12, uint16_t)
+ * (enc_intra_prediction.c:60, :241) leave in dst, bit for bit.  Descriptors sit at the level of that function's parameter list: the availability derivation
+ * (svt_aom_intra_has_top_right and the like), get_filt_type and palette are the caller's.  Everything from the neighbour pointers to dst happens in the kernel: the
+ * need_* flags with their overrides, the constant fill when the needed edge is absent (base +- 1 or the first neighbour), copy + replicate extension, the above-left
+ * rule, filter_intra_edge_corner, both svt_av1_filter_intra_edge calls (strengths and n_px as written there), both upsamplings, then z1 / z2 / z3, V / H at 90 / 180,
+ * the DC variant selected by [n_left_px > 0][n_top_px > 0], SMOOTH / SMOOTH_V / SMOOTH_H, PAETH or the recursive filter-intra.  The prepared edges never reach memory.
+ * READABLE EXTENT: top is read only inside [-1, n_top_px + n_topright_px), [-1] only when n_top_px > 0 and n_left_px > 0, nothing when n_top_px == 0; left only at
+ * i * left_stride for i in [0, n_left_px + n_bottomleft_px).
+ * planes.base[] are device pointers, passed by value; dst_base and descs are device pointers; dst may be one of the planes (the blocks of a launch are independent).
+ * INVALID DESCRIPTORS (a size outside the 19 of TX_SIZES_ALL; mode > 12; |angle_delta| > 3; filter_intra_mode > 5, or < 5 with w or h above 32; n_top_px > w,
+ * n_left_px > h, n_topright_px > w or > 0 without n_top_px == w, n_bottomleft_px > h or > 0 without n_left_px == h; disable_edge_filter or filt_type above 1; a plane
+ * index >= 32 or without a base) never fault: status == NULL / != NULL and the return value exactly as svt_hip_inter_pred_batch. */
+typedef struct SvtHipIntraPredPlanes { const void *base[32]; } SvtHipIntraPredPlanes;
+typedef struct SvtHipIntraPredDesc {
+    uint64_t top_off;        /* samples from planes.base[top_plane]: where top_neigh_array points; the above-left corner is at [-1] */
+    uint64_t left_off;       /* samples from planes.base[left_plane]: left neighbour i is at left_off + i * left_stride */
+    uint64_t dst_off;        /* samples from dst_base */
+    uint32_t left_stride;    /* 1 = the reference's neighbour array; a picture stride reads a column of a reconstructed plane in place */
+    uint32_t dst_stride;
+    uint8_t  top_plane, left_plane;
+    uint8_t  w, h;           /* tx_size_wide / tx_size_high of one of the 19 TxSize values */
+    uint8_t  mode;           /* PredictionMode 0 .. 12: DC_PRED .. PAETH_PRED */
+    int8_t   angle_delta;    /* -3 .. 3; ignored for non-directional modes, as the C does */
+    uint8_t  filter_intra_mode; /* FilterIntraMode 0 .. 4, or 5 = FILTER_INTRA_MODES = off */
+    uint8_t  n_top_px, n_topright_px, n_left_px, n_bottomleft_px;
+    uint8_t  disable_edge_filter;
+    uint8_t  filt_type;      /* what get_filt_type(xd, plane) returns: 1 when the above or the left neighbour block is smooth */
+    uint8_t  pad[3];
+} SvtHipIntraPredDesc; /* 48 bytes */
+int svt_hip_intra_pred_batch(SvtHipIntraPredPlanes planes, void *dst_base, const SvtHipIntraPredDesc *descs, uint32_t n, int bit_depth, uint8_t *status,
+                             void *stream);
+/* Chroma from luma, one wave per descriptor: svt_cfl_luma_subsampling_420_{lbd,hbd} of the 2w x 2h luma block at luma_off -> svt_subtract_average with
+ * round_offset = (w * h) >> 1, num_pel_log2 = log2 w + log2 h -> svt_cfl_predict_{lbd,hbd} for one or two chroma targets that share the AC values (Cb and Cr).
+ * The Q3 AC buffer never reaches memory.  w x h: the 14 sizes of the reference's CFL_SUB_AVG_FN table (4 .. 32 either way without 4x32 and 32x4).  The DC prediction
+ * of target t is read at planes.base[pred_plane[t]] + pred_off[t]; dst_base + dst_off[t] may be that very location (the encoder predicts in place,
+ * product_coding_loop.c:3906).  READABLE EXTENT: luma inside 2w x 2h, each DC prediction inside w x h.  Invalid descriptors (size, n_targets not 1 / 2, planes) are
+ * handled like svt_hip_intra_pred_batch's. */
+typedef struct SvtHipCflPredDesc {
+    uint64_t luma_off;
+    uint64_t pred_off[2], dst_off[2];
+    uint32_t luma_stride, pred_stride[2], dst_stride[2];
+    int16_t  alpha_q3[2];    /* signed, what cfl_idx_to_alpha returns */
+    uint8_t  luma_plane, pred_plane[2];
+    uint8_t  w, h;           /* the chroma block */
+    uint8_t  n_targets;      /* 1 or 2 */
+    uint8_t  pad[2];
+} SvtHipCflPredDesc; /* 72 bytes */
+int svt_hip_cfl_pred_batch(SvtHipIntraPredPlanes planes, void *dst_base, const SvtHipCflPredDesc *descs, uint32_t n, int bit_depth, uint8_t *status, void *stream);
+/* single-call forms with the reference's prototypes (exported, NOT installed by svt_hip_setup_rtcd: INTEGRATION.md).  Host pointers; each copies exactly the
+ * index range of above / left its C function can read: z1 above [0, (bw + bh - 1) << upsample_above]; z3 left [0, (bw + bh - 1) << upsample_left]; z2 above
+ * [-(1 << upsample_above), (bw - 1) << upsample_above] and left [-(1 << upsample_left), (bh - 1) << upsample_left]; filter-intra above [-1, w - 1], left [0, h - 1].
+ * ACCEPTED RANGE, outside of which a form returns having written nothing: bw x bh one of the 19 sizes; upsample flags 0 / 1, 1 only with bw + bh <= 16; dx, dy in
+ * 1 .. 65535; bd 10 or 12 in the highbd forms; tx_size with w, h <= 32 and mode 0 .. 4 (filter-intra); width x height (chroma; luma / 2 for the subsampling forms)
+ * in the CFL_SUB_AVG_FN table, bit_depth 8 .. 12.  SvtHipTxSize is TxSize (definitions.h:849-878), a packed one-byte enum. */
+#ifdef SVT_HIP_REFERENCE_TYPES
+typedef TxSize SvtHipTxSize;
+#else
+typedef uint8_t SvtHipTxSize;
+#endif
+/* svt_av1_dr_prediction_z1 / z2 / z3 (common_dsp_rtcd.h:581-586) -> svt_av1_dr_prediction_z{1,2,3}_c (intra_prediction.c:314-413) */
+void svt_av1_dr_prediction_z1_hip(uint8_t *dst, ptrdiff_t stride, int32_t bw, int32_t bh, const uint8_t *above, const uint8_t *left, int32_t upsample_above, int32_t dx,
+                                  int32_t dy);
+void svt_av1_dr_prediction_z2_hip(uint8_t *dst, ptrdiff_t stride, int32_t bw, int32_t bh, const uint8_t *above, const uint8_t *left, int32_t upsample_above,
+                                  int32_t upsample_left, int32_t dx, int32_t dy);
+void svt_av1_dr_prediction_z3_hip(uint8_t *dst, ptrdiff_t stride, int32_t bw, int32_t bh, const uint8_t *above, const uint8_t *left, int32_t upsample_left, int32_t dx,
+                                  int32_t dy);
+/* svt_av1_highbd_dr_prediction_z1 / z3 (common_dsp_rtcd.h:587-590), z2 (:101-102) -> the `_c` functions (intra_prediction.c:2303-2370, C_DEFAULT/intra_prediction_c.c:58) */
+void svt_av1_highbd_dr_prediction_z1_hip(uint16_t *dst, ptrdiff_t stride, int32_t bw, int32_t bh, const uint16_t *above, const uint16_t *left, int32_t upsample_above,
+                                         int32_t dx, int32_t dy, int32_t bd);
+void svt_av1_highbd_dr_prediction_z2_hip(uint16_t *dst, ptrdiff_t stride, int32_t bw, int32_t bh, const uint16_t *above, const uint16_t *left, int32_t upsample_above,
+                                         int32_t upsample_left, int32_t dx, int32_t dy, int32_t bd);
+void svt_av1_highbd_dr_prediction_z3_hip(uint16_t *dst, ptrdiff_t stride, int32_t bw, int32_t bh, const uint16_t *above, const uint16_t *left, int32_t upsample_left,
+                                         int32_t dx, int32_t dy, int32_t bd);
+/* svt_av1_filter_intra_predictor (common_dsp_rtcd.h:91-92) -> svt_av1_filter_intra_predictor_c (C_DEFAULT/filterintra_c.c:70) */
+void svt_av1_filter_intra_predictor_hip(uint8_t *dst, ptrdiff_t stride, SvtHipTxSize tx_size, const uint8_t *above, const uint8_t *left, int32_t mode);
+/* svt_cfl_predict_lbd / _hbd (common_dsp_rtcd.h:79-82) -> C_DEFAULT/cfl_c.c:25, :44; pred_buf_q3 in rows of CFL_BUF_LINE = 32; dst may be pred */
+void svt_cfl_predict_lbd_hip(const int16_t *pred_buf_q3, uint8_t *pred, int32_t pred_stride, uint8_t *dst, int32_t dst_stride, int32_t alpha_q3, int32_t bit_depth,
+                             int32_t width, int32_t height);
+void svt_cfl_predict_hbd_hip(const int16_t *pred_buf_q3, uint16_t *pred, int32_t pred_stride, uint16_t *dst, int32_t dst_stride, int32_t alpha_q3, int32_t bit_depth,
+                             int32_t width, int32_t height);
+/* svt_cfl_luma_subsampling_420_lbd / _hbd (common_dsp_rtcd.h:83-89) -> intra_prediction.c:420, :435; width x height are LUMA samples */
+void svt_cfl_luma_subsampling_420_lbd_hip(const uint8_t *input, int32_t input_stride, int16_t *output_q3, int32_t width, int32_t height);
+void svt_cfl_luma_subsampling_420_hbd_hip(const uint16_t *input, int32_t input_stride, int16_t *output_q3, int32_t width, int32_t height);
+
 /* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
 #define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
 #define SVT_HIP_BLOCK_MEAN_PREC_SUB  1

@@ -291,6 +291,33 @@ for _n in CONVOLVE_FORMS:
     PROTOTYPES["svt_av1_highbd_%s_hip" % _n] = (None, _CV + [C.c_int32])
 
 
+# AV1 intra prediction (csrc/intrapred.hip): SvtHipIntraPredPlanes, SvtHipIntraPredDesc, SvtHipCflPredDesc
+class IntraPredPlanes(C.Structure):
+    _fields_ = [("base", vp * 32)]
+
+
+FILTER_INTRA_OFF = 5  # FILTER_INTRA_MODES
+INTRA_DESCS_PER_WORKGROUP = 16  # descriptors one workgroup of svt_hip_intra_pred_batch flattens into its tile list
+IntraPredDesc = np.dtype([("top_off", "<u8"), ("left_off", "<u8"), ("dst_off", "<u8"), ("left_stride", "<u4"), ("dst_stride", "<u4"), ("top_plane", "u1"),
+                          ("left_plane", "u1"), ("w", "u1"), ("h", "u1"), ("mode", "u1"), ("angle_delta", "i1"), ("filter_intra_mode", "u1"), ("n_top_px", "u1"),
+                          ("n_topright_px", "u1"), ("n_left_px", "u1"), ("n_bottomleft_px", "u1"), ("disable_edge_filter", "u1"), ("filt_type", "u1"),
+                          ("pad", "u1", (3,))])
+CflPredDesc = np.dtype([("luma_off", "<u8"), ("pred_off", "<u8", (2,)), ("dst_off", "<u8", (2,)), ("luma_stride", "<u4"), ("pred_stride", "<u4", (2,)),
+                        ("dst_stride", "<u4", (2,)), ("alpha_q3", "<i2", (2,)), ("luma_plane", "u1"), ("pred_plane", "u1", (2,)), ("w", "u1"), ("h", "u1"),
+                        ("n_targets", "u1"), ("pad", "u1", (2,))])
+assert IntraPredDesc.itemsize == 48 and CflPredDesc.itemsize == 72 and C.sizeof(IntraPredPlanes) == 256
+PROTOTYPES["svt_hip_intra_pred_batch"] = (C.c_int, [IntraPredPlanes, vp, vp, C.c_uint32, C.c_int, vp, vp])
+PROTOTYPES["svt_hip_cfl_pred_batch"] = (C.c_int, [IntraPredPlanes, vp, vp, C.c_uint32, C.c_int, vp, vp])
+_DR = [vp, C.c_ssize_t, C.c_int32, C.c_int32, vp, vp, C.c_int32, C.c_int32, C.c_int32]
+for _z in (1, 2, 3):
+    PROTOTYPES["svt_av1_dr_prediction_z%d_hip" % _z] = (None, _DR + ([C.c_int32] if _z == 2 else []))
+    PROTOTYPES["svt_av1_highbd_dr_prediction_z%d_hip" % _z] = (None, _DR + ([C.c_int32] if _z == 2 else []) + [C.c_int32])
+PROTOTYPES["svt_av1_filter_intra_predictor_hip"] = (None, [vp, C.c_ssize_t, C.c_uint8, vp, vp, C.c_int32])
+for _n in ("lbd", "hbd"):
+    PROTOTYPES["svt_cfl_predict_%s_hip" % _n] = (None, [vp, vp, C.c_int32, vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32])
+    PROTOTYPES["svt_cfl_luma_subsampling_420_%s_hip" % _n] = (None, [vp, C.c_int32, vp, C.c_int32, C.c_int32])
+
+
 # picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
 BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
 VarBoostFrame = np.dtype([("normalized_base_q_idx", "<i4"), ("min_qindex", "<i4"), ("max_qindex", "<i4"), ("reserved", "<i4")])
