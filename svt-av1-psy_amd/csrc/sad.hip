@@ -225,12 +225,39 @@ __device__ __forceinline__ uint32_t dpp_scatter_sum_quads(const uint32_t (&v)[4]
 // QLDS (the wave kernel): the 16x16 sum of a quad is formed on the LDS pipe, which the search leaves nearly idle, instead of four DPP adds
 // and a v_perm.  `qsum` is the wave's own 16 slots of 8 bytes, one per quad: the slot is zeroed, every lane of the quad adds its four packed u16 SADs with ONE
 // 64-bit atomicAdd whose result is unused (ds_add_u64; no u16 lane can carry: 4 * 16 320 = 65 280), and lane q reads u16 number q back, zero extended.  The value
-// is consumed one step late, so that no wait for the LDS sits between a step's qsads and its tail; only the last step of a group is waited for.  This crosses
+// is consumed a step or two late, so that no wait for the LDS sits between a step's qsads and its tail; only the last step of a group is waited for.  This crosses
 // lanes: the LDS queue of a wave is in order on the hardware, and the fence + wave barrier keep the compiler from reordering (and order the emulator's lanes).
+// QLDS without SUB (`PAIRG` below; with SUB a step is half as long and the form before this one is kept, instruction for instruction) also pairs work over the two
+// step groups of a ring block (steps 0-3 = A, steps 4-7 = B; fourth cut in DESIGN.md section 4.1): the 16x16 keys are formed two
+// steps at a time (one v_min3 for two), the last step of a whole group is taken by a scalar branch instead of a pick, and where B has a 32x32 level of its own
+// (two steps or more) the levels of A wait for it: one v_min3 takes both 32x32 keys, and the two 32x32 registers go through the row / half swaps TOGETHER
+// (sum_rows_pair), after which even rows hold the 64x64 sum of A and odd rows that of B -- one key + min for both.  Which one a lane holds is a constant of the
+// lane: B lies four rows = 256 positions further (bit 8; a ring block starts at a multiple of eight rows), ORed in behind the loops.  An A without such a B keeps
+// the single form, with a 64x64 tracker of its own (all four rows hold its sum there).
 constexpr int ME_WAVE_QSUM_DW = 32; // dwords of a wave's quad-sum slots, behind its window
 __device__ __forceinline__ void me_lds_order() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+}
+// 64x64 sums of two 32x32 registers in one pass over the row / half swaps (the four rows of the wave are the four 32x32 blocks).  Out: lanes of rows 0 and 2 hold the
+// sum of a over the four rows, lanes of rows 1 and 3 that of b.  v_permlane16_swap exchanges the odd rows of its first operand with the even rows of its second:
+// {a0 b0 a2 b2} and {a1 b1 a3 b3}; their sum is {a01 b01 a23 b23}, and the half swap of that sum with itself adds rows r and r ^ 2.
+__device__ __forceinline__ uint32_t sum_rows_pair(const uint32_t a, const uint32_t b) {
+#ifdef SVT_HIP_EMU
+    // the row assignment spelled out: row r of the result reads a (r even) or b (r odd) at the same position of all four rows
+    const int l = (int)(threadIdx.x & 63);
+    uint32_t  t = 0;
+    for (int r = 0; r < 4; r++) {
+        const uint32_t ar = (uint32_t)__shfl((int)a, (l & 15) + 16 * r), br = (uint32_t)__shfl((int)b, (l & 15) + 16 * r);
+        t += ((l >> 4) & 1) ? br : ar;
+    }
+    return t;
+#else
+    const auto     x16 = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    const uint32_t two = x16[0] + x16[1];
+    const auto     x32 = __builtin_amdgcn_permlane32_swap(two, two, false, false);
+    return x32[0] + x32[1];
+#endif
 }
 template <bool SUB, bool FULL, int PITCH = ME_PITCH, bool QLDS = false>
 __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ win, const uint32_t (&s)[8][2], int Wt, int Ht, int g0, int gstep, int l,
@@ -248,6 +275,8 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
     // one (261 120 and 1 044 480) and still fit the 21 bits a key has for the SAD, so its key loses against the key of any step that exists.
     constexpr uint32_t NO_STEP = 0x1ffffu;
     uint32_t       b16 = 0xffffffffu, b32 = 0xffffffffu, b64 = 0xffffffffu; // winners with the lane-constant position bits still missing
+    constexpr bool PAIRG = QLDS && !SUB; // the two step groups of a ring block share their levels (above); what is marked PAIRG below is dead without it
+    uint32_t       b64s  = 0xffffffffu;  // PAIRG only: the 64x64 winner of the groups evaluated alone (b64: of the pairs of groups)
     // A last group of ONE step (Ht % 4 == 1) does not pay a reduce-scatter with three sentinels: it is pooled over up to four x groups.  Behind the y loop of an
     // x group the step's 32x32 sum is all-reduced over the row (two adds) and kept by the lanes of quad kc only, kc = the x group's number within the pool, so
     // that after four x groups quad c holds the remainder step of x group c and ONE pass over the 32x32 / 64x64 levels serves them all.  The lane-constant part
@@ -267,6 +296,10 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
             const uint32_t k16 = (sad16 << KEY_POS_BITS) | at;
             b16 = umin32(b16, FULL ? k16 : (k16 | invq));
         };
+        auto track16x2 = [&](const uint32_t sad16a, const uint32_t sad16b, const uint32_t at) { // the keys of two consecutive steps, the first at `at`
+            const uint32_t ka = (sad16a << KEY_POS_BITS) | at, kb = (sad16b << KEY_POS_BITS) | (at + ME_TW);
+            b16 = FULL ? umin32(umin32(b16, ka), kb) : umin32(b16, umin32(ka, kb) | invq); // (invq is nothing or all ones: it commutes with the minimum)
+        };
         // 8-row ring; each row is kept as the two overlapping 8-byte windows v_qsad_pk_u16_u8 consumes
         U64A4 ra[8], rb[8];
 #pragma unroll
@@ -276,6 +309,7 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
         }
         uint32_t pos = (uint32_t)(4 * g); // wave-uniform: the keys take it as a scalar operand
         uint32_t v0  = 0;                 // the 16x16 SADs of the first step of the group walked last
+        uint32_t s32a = 0;                // PAIRG only: the 32x32 sums of group A while its levels wait for group B
         for (int yb = 0; yb < Ht; yb += 8) {
             const uint32_t* rowp = colp + (yb + 7) * PITCH;
 #pragma unroll
@@ -307,8 +341,12 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
                                 me_lds_order();
                                 atomicAdd(qslot, acc);
                                 me_lds_order();
-                                v[j] = *qmine; // lane q of the quad takes position q; consumed at the next step, or behind the group
-                                if (j > 0) track16(v[j - 1], pos - ME_TW);
+                                v[j] = *qmine; // lane q of the quad takes position q; consumed at the next step (PAIRG: two steps at a time), or behind the group
+                                if (PAIRG) {
+                                    if (j == 2) track16x2(v[0], v[1], pos - 2 * ME_TW);
+                                } else if (j > 0) {
+                                    track16(v[j - 1], pos - ME_TW);
+                                }
                             } else {
                                 // 16x16 = the quad's four 8x8 (u16 lanes: 4 * 16320 < 65536, so plain adds never carry)
                                 const uint32_t tlo = dpp_add_quad_xor2(dpp_add_quad_xor1(lo));
@@ -320,12 +358,48 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
                             pos += ME_TW;
                         }
                     }
-                    if (QLDS) { // the group's last step: the one sum that is waited for
+                    if (PAIRG) { // what the steps left over; the group's last sum is the one that is waited for.  Scalar branches (`left` is wave-uniform): as selects,
+                                 // every side would run in every group; the empty asm statements keep the compiler from converting them (tools/me_wave_census.py
+                                 // lists the sides as "leftover" blocks and says so when it finds none).
+                        const int left = Ht - (yb + 4 * h); // steps of the column from this group on
+                        if (left >= 4) {
+                            asm volatile("");
+                            track16x2(v[2], v[3], pos - 2 * ME_TW);
+                        } else if (left == 3) {
+                            asm volatile("");
+                            track16(v[2], pos - ME_TW);
+                        } else if (left == 2) {
+                            asm volatile("");
+                            track16x2(v[0], v[1], pos - 2 * ME_TW);
+                        } else {
+                            track16(v[0], pos - ME_TW);
+                        }
+                    } else if (QLDS) { // the group's last step: the one sum that is waited for
                         const int left = Ht - (yb + 4 * h);
                         track16(left >= 4 ? v[3] : (left == 3 ? v[2] : (left == 2 ? v[1] : v[0])), pos - ME_TW);
                     }
                     v0 = v[0];
-                    if (yb + 4 * h + 1 < Ht) { // (a group of one step goes into the pool, below)
+                    if (PAIRG) {
+                        const int      left   = Ht - (yb + 4 * h);
+                        const bool     paired = left >= 6 - 4 * h; // group B of this ring block has a 32x32 level of its own
+                        const uint32_t gposa  = (uint32_t)(4 * g + ME_TW * yb);
+                        if (h == 0 && left >= 2) {
+                            s32a = dpp_scatter_sum_quads(v);
+                            if (!paired) { // group A alone: all four rows hold its 64x64 sum
+                                const uint32_t k32 = (s32a << KEY_POS_BITS) | gposa;
+                                b32 = umin32(b32, FULL ? k32 : (k32 | invq));
+                                const uint32_t k64 = (sum_rows_pair(s32a, s32a) << KEY_POS_BITS) | gposa;
+                                b64s = umin32(b64s, FULL ? k64 : (k64 | invq));
+                            }
+                        }
+                        if (h == 1 && paired) { // both groups: quad c stands for step c of its group, even rows for A at 64x64, odd rows for B
+                            const uint32_t s32b = dpp_scatter_sum_quads(v);
+                            const uint32_t k32a = (s32a << KEY_POS_BITS) | gposa, k32b = (s32b << KEY_POS_BITS) | (gposa + 4 * ME_TW);
+                            b32 = FULL ? umin32(umin32(b32, k32a), k32b) : umin32(b32, umin32(k32a, k32b) | invq);
+                            const uint32_t k64 = (sum_rows_pair(s32a, s32b) << KEY_POS_BITS) | gposa;
+                            b64 = umin32(b64, FULL ? k64 : (k64 | invq));
+                        }
+                    } else if (yb + 4 * h + 1 < Ht) { // (a group of one step goes into the pool, below)
                         // 32x32 = 4 quads of a 16-lane row, 64x64 = 4 rows: once for the group; quad c now stands for step c
                         const uint32_t gpos  = (uint32_t)(4 * g + ME_TW * (yb + 4 * h));
                         const uint32_t sad32 = dpp_scatter_sum_quads(v);
@@ -362,7 +436,8 @@ __device__ __forceinline__ void me_search_strips(const uint32_t* __restrict__ wi
     // A lane that saw no valid position keeps all ones.
     best16 = umin32(best16, b16 | (uint32_t)q);
     best32 = umin32(best32, b32 | (uint32_t)(q | (c << 6)));
-    best64 = umin32(best64, b64 | (uint32_t)(q | (c << 6)));
+    best64 = umin32(best64, b64 | (uint32_t)(q | (c << 6) | (PAIRG ? ((l << 4) & 256) : 0))); // PAIRG: odd rows tracked group B of the pairs, four rows further
+    if (PAIRG) best64 = umin32(best64, b64s | (uint32_t)(q | (c << 6)));
     // the pooled remainder steps: x = q, x group within the pool = c (all ones where there was no pool)
     best32 = umin32(best32, b32p | (uint32_t)(q | (4 * gstep * c)));
     best64 = umin32(best64, b64p | (uint32_t)(q | (4 * gstep * c)));

@@ -15,7 +15,15 @@ Compiles sad.hip for gfx950 with the flags of csrc/Makefile plus `-S --cuda-devi
                                   of two to four steps
                        pool add : a block with full-row v_add_u32_dpp row_ror and neither qsad nor swap = a last group of ONE step (H % 4 == 1): its 32x32
                                   sum goes into the pool of up to four x groups
-                       pool     : a block with v_permlane32_swap and no reduce-scatter = the 32x32 / 64x64 levels of a pool, once per four x groups
+                       pool     : a block with v_permlane32_swap, no reduce-scatter and the refill of the pool register (0x7ffff) = the 32x32 / 64x64 levels of
+                                  a pool, once per four x groups
+                     A build that pairs the two step groups of a ring block (steps 0-3 = A, 4-7 = B; it has a reduce-scatter block WITHOUT a swap) is modelled
+                     per ring block of eight steps instead of per group:
+                       scatter  : the reduce-scatter of group A alone, whose levels wait for group B (A of two steps or more)
+                       group    : reduce-scatter of B + both 32x32 keys + the row / half swaps on both registers (B of two steps or more)
+                       alone    : a block with the swaps and neither reduce-scatter nor pool refill = the levels of an A without such a B
+                       leftover : the blocks behind the steps of a group that key the 16x16 sums not yet taken, one of four scalar-branch sides: two sums
+                                  (a group of four or two steps; the dearer sides) or one (three steps, one step; the cheaper sides)
   final            : from the first v_min_u32_dpp on: minima over the lanes, the cross-lane read (ds_bpermute, counted apart: LDS pipe) and the two store
                      passes.  The stores of an empty search area (the loop at the very end) are laid out here too; no wave with an area runs them.
 
@@ -27,6 +35,10 @@ LDS instructions (every ds_* but ds_bpermute; atomics = ds_min / ds_add, counted
 the quad sums of me_search_strips run on that pipe instead of the VALU, and four SIMDs share it.  The metadata line gives the static LDS bytes; the
 launcher's dynamic bytes per workgroup and the workgroups per CU they allow (160 KB per CU) are printed for the area.
 SQ_INSTS_VALU / SQ_WAVES and SQ_INSTS_LDS / SQ_WAVES of a counter pass on the GPU are the exact figures; this script is the desk check before that pass.
+The model of a build that pairs step groups is approximate: its blocks are told apart by text patterns (the pool's refill constant 0x7ffff, a key's shift by 11), and
+the sides of its scalar branches are smaller blocks whose copies and sentinel moves land in "prologue and loop control" or in a step's tail as the compiler pleases.
+Against the counters it missed the change of the commit that introduced the pairing by about 20 instructions per wave (-42 predicted, -64 measured at 16x9:
+profiles/me_wave_pairs_timing.txt).
 """
 import argparse
 import os
@@ -82,7 +94,13 @@ def blocks_of(lines, name):
         swap = any(o.startswith("v_permlane32_swap") for o in b["ops"])
         scatter = any(t.startswith("v_add_u32_dpp") and "bank_mask:0x3" in t for t in b["txt"])
         b["grp"] = swap and scatter
-        b["pool"] = swap and not scatter
+        refill = any(t.startswith("v_mov_b32") and t.endswith("0x7ffff") for t in b["txt"])
+        b["pool"] = swap and not scatter and refill
+        b["alone"] = swap and not scatter and not refill  # (only a build that pairs step groups has such a block)
+        b["scat"] = scatter and not swap
+        dpp = any("_dpp" in o for o in b["ops"])
+        b["left"] = (not b["qsad"] and not swap and not dpp and any(o.startswith(("v_min_u32", "v_min3_u32")) for o in b["ops"])
+                     and any(re.match(r"v_lshl_or_b32 \S+ \S+ 11,", t) for t in b["txt"]))
         b["padd"] = not swap and not b["qsad"] and any(t.startswith("v_add_u32_dpp") and "row_ror" in t and "bank_mask:0xf" in t for t in b["txt"])
         b["fin"] = any(o.startswith("v_min_u32_dpp") for o in b["ops"])
         b["bperm"] = sum(o.startswith("ds_bpermute") for o in b["ops"])
@@ -158,6 +176,7 @@ def main():
         groups -= 1
     n_padd, n_pool = (1, -(-G // 4)) if pooled and H % 4 == 1 else (0, 0)
     total, lds_total = {}, {}
+    pairing = any(b["scat"] for b in bl)  # the two step groups of a ring block share their 32x32 / 64x64 levels
     for k, s0 in enumerate(starts):
         s1 = starts[k + 1] if k + 1 < len(starts) else last_search + 1
         inst = bl[s0:s1]
@@ -165,7 +184,7 @@ def main():
         grp = [b for b in inst if b["grp"] and not b["qsad"]]
         padd = [b["valu"] for b in inst if b["padd"]] or [0]
         pool = [b["valu"] for b in inst if b["pool"]] or [0]
-        other = [b for b in inst if not b["qsad"] and not b["grp"] and not b["padd"] and not b["pool"]]
+        other = [b for b in inst if not b["qsad"] and not b["grp"] and not b["padd"] and not b["pool"] and not (pairing and (b["scat"] or b["alone"] or b["left"]))]
         tails = [b["valu"] - b["qsad"] for b in steps]
         gt = [b["valu"] for b in grp] or [0]  # (no group blocks: the levels are part of every step)
         q = steps[0]["qsad"]
@@ -177,13 +196,33 @@ def main():
                       + n_padd * mean([b["lds"] for b in inst if b["padd"]] or [0])) + n_pool * mean([b["lds"] for b in inst if b["pool"]] or [0])
         lds_total[k] = (lds_step, atom_step, lds_ex, G * H * atom_step)
         ex = [G * (pro + H * (q + f(tails)) + groups * f(gt) + n_padd * f(padd)) + n_pool * f(pool) for f in (min, mean, max)]
+        if pairing:  # per ring block: what its groups A and B of nA and nB steps run (a group of one step goes to the pool)
+            scat, alone = [b["valu"] for b in inst if b["scat"]] or [0], [b["valu"] for b in inst if b["alone"]] or [0]
+            left = [b["valu"] for b in inst if b["left"] and b["valu"]] or [0]
+            lv = [0, 0, 0]
+            for yb in range(0, H, 8):
+                nA, nB = min(4, H - yb), max(0, min(4, H - yb - 4))
+                for m, f in enumerate((min, mean, max)):
+                    lv[m] += sum((max(left) if n in (2, 4) else min(left)) for n in (nA, nB) if n)
+                    if nA >= 2:
+                        lv[m] += f(scat) + (f(gt) if nB >= 2 else f(alone))
+            ex = [G * (pro + H * (q + f(tails)) + lv[m] + n_padd * f(padd)) + n_pool * f(pool) for m, f in enumerate((min, mean, max))]
+            print("search instance %d : paired step groups: scatter of A %s, levels of A + B %s, of A alone %s, leftover 16x16 keys of a group %s (dearer: two sums)" %
+                  (k, sorted(scat), sorted(gt), sorted(alone), sorted(left)))
+            nleft = len([b for b in inst if b["left"] and b["valu"]])
+            if nleft < 4:  # (the source keeps the four sides apart with empty asm statements; as selects they would all run in every group)
+                print("                    WARNING: %d leftover blocks, 4 or more expected: the compiler has turned scalar-branch sides into selects" % nleft)
         total[k] = (sum(tails), ex)
         print("search instance %d : %d step blocks, tail VALU per step %s (mean %.1f) + %d qsad; %d group blocks, VALU per group of four steps %s (mean %.1f); "
               "prologue and loop control %d per x group" % (k, len(steps), sorted(tails), mean(tails), q, len(grp), sorted(gt), mean(gt), pro))
         if pooled:
             print("                    pool add (a last group of one step) %s per x group, pool %s per four x groups" % (sorted(padd), sorted(pool)))
-        print("                    executed at %dx%d: %d x groups x (%d + %d steps x (%d + tail) + %d groups x group + %d x pool add) + %d x pool = %.0f  [%d, %d]" %
-              (W, H, G, pro, H, q, groups, n_padd, n_pool, ex[1], ex[0], ex[2]))
+        if pairing:
+            print("                    executed at %dx%d: %d x groups x (%d + %d steps x (%d + tail) + %.0f for the levels and leftovers of %d ring blocks + %d x pool add) "
+                  "+ %d x pool = %.0f  [%d, %d]" % (W, H, G, pro, H, q, lv[1], -(-H // 8), n_padd, n_pool, ex[1], ex[0], ex[2]))
+        else:
+            print("                    executed at %dx%d: %d x groups x (%d + %d steps x (%d + tail) + %d groups x group + %d x pool add) + %d x pool = %.0f  [%d, %d]" %
+                  (W, H, G, pro, H, q, groups, n_padd, n_pool, ex[1], ex[0], ex[2]))
     final = bl[last_search + 1:]
     back = [idx[t] - (last_search + 1) for i, b in enumerate(final) for t in b["to"] if t in idx and last_search + 1 <= idx[t] <= last_search + 1 + i]
     empty = final[max(min(back) - 1, 0):] if back else []  # the store loop of an empty area and its preheader
