@@ -1005,6 +1005,150 @@ void svt_cfl_predict_hbd_hip(const int16_t *pred_buf_q3, uint16_t *pred, int32_t
 void svt_cfl_luma_subsampling_420_lbd_hip(const uint8_t *input, int32_t input_stride, int16_t *output_q3, int32_t width, int32_t height);
 void svt_cfl_luma_subsampling_420_hbd_hip(const uint16_t *input, int32_t input_stride, int16_t *output_q3, int32_t width, int32_t height);
 
+/* ------------------------------------------- AV1 masked prediction: blends (inter-intra, OBMC, wedge), wedge search (csrc/maskpred.hip) ------ */
+/* One launch, n blocks of mixed sizes: dst = AOM_BLEND_A64(mask, src0, src1) = ROUND_POWER_OF_TWO(m * src0 + (64 - m) * src1, 6), bit for bit what
+ *   kind A64_MASK  svt_aom_blend_a64_mask_c / svt_aom_highbd_blend_a64_mask_c (blend_a64_mask.c:201, :248) compute, with subw, subh in {0, 1}: the 2 x 2 mask average is
+ *                  ROUND_POWER_OF_TWO(sum of four, 2), the two 1-D averages are AOM_BLEND_AVG;
+ *   kind HMASK     svt_aom_blend_a64_hmask_c (:323) / svt_aom_highbd_blend_a64_hmask_16bit_c (inter_prediction.c:2374): mask[column];
+ *   kind VMASK     svt_aom_blend_a64_vmask_c (:302) / svt_aom_highbd_blend_a64_vmask_16bit_c: mask[row].
+ * THE ORDER (mask, src0, src1) IS THE REFERENCE'S: the mask weighs src0.  For inter-intra pass the INTRA prediction as src0 and the INTER prediction as src1, exactly as
+ * svt_aom_combine_interintra does (inter_prediction.c:2341-2372); for OBMC src0 is the block's own prediction and src1 the neighbour's (enc_inter_prediction.c:1461, :1508).
+ * Mask source:
+ *   EXPLICIT   mask_off, mask_stride into mask_base (device bytes; HMASK / VMASK read w / h bytes at mask_off);
+ *   WEDGE      (A64_MASK only) the mask svt_aom_get_contiguous_soft_mask(wedge_index, wedge_sign, bsize) returns, stride block_size_wide[bsize]: a chroma block of a
+ *              4:2:0 picture reads the luma-sized mask with subw = subh = 1.  bsize is one of the nine BlockSize values with wedge bits (8x8, 8x16, 16x8, 16x16,
+ *              16x32, 32x16, 32x32, 8x32, 32x8); (w << subw, h << subh) must not exceed its dimensions.  The table is generated on the device by svt_hip_maskpred_prepare, or by the
+ *              first call of this section on that device, which then waits for it once (one stream synchronisation, also with a status array: call
+ *              svt_hip_maskpred_prepare first where that matters, e.g. before a stream capture);
+ *   SMOOTH_II  (A64_MASK only, subw = subh = 0) the mask of build_smooth_interintra_mask(plane_bsize = bsize, mode = ii_mode 0 .. 3: II_DC_PRED, II_V_PRED, II_H_PRED,
+ *              II_SMOOTH_PRED) (inter_prediction.c:2144), computed in the kernel; block_size_wide / high[bsize] must equal w, h;
+ *   OBMC       (HMASK / VMASK only) svt_av1_get_obmc_mask(w) for HMASK, (h) for VMASK: lengths 1, 2, 4, 8, 16, 32.
+ * dst may alias src0 or src1 at the same position and stride (the reference's IMPLIES assertion): a lane reads the samples it writes before it writes them, every sample
+ * is written exactly once.  OBMC blends in place.
+ * READABLE EXTENT, exactly what the C reads: w x h of each source; (w << subw) x (h << subh) of a 2-D mask; w (HMASK) or h (VMASK) bytes of a 1-D mask.
+ * planes.base[] are device pointers (uint8_t samples at bit_depth 8, uint16_t at 10 and 12), passed by value; dst_base, mask_base and descs are device pointers.
+ * INVALID DESCRIPTORS (w or h not one of 1, 2, 4 .. 128; kind > 2; mask_src > 3; subw or subh > 1; a plane index >= 32 or without a base; EXPLICIT without mask_base;
+ * WEDGE with another kind, a bsize that is not one of the nine, wedge_index > 15, wedge_sign > 1 or a block larger than the mask; SMOOTH_II with another kind, a
+ * sub-sampling, ii_mode > 3 or a bsize whose dimensions are not w x h; OBMC with kind A64_MASK or a length above 32) never fault: status == NULL / != NULL and the return
+ * value exactly as svt_hip_inter_pred_batch. */
+#define SVT_HIP_BLEND_A64_MASK 0
+#define SVT_HIP_BLEND_HMASK    1
+#define SVT_HIP_BLEND_VMASK    2
+#define SVT_HIP_MASK_EXPLICIT  0
+#define SVT_HIP_MASK_WEDGE     1
+#define SVT_HIP_MASK_SMOOTH_II 2
+#define SVT_HIP_MASK_OBMC      3
+typedef struct SvtHipBlendPlanes { const void *base[32]; } SvtHipBlendPlanes;
+typedef struct SvtHipBlendDesc {
+    uint64_t src_off[2];     /* samples from planes.base[plane[k]] */
+    uint64_t dst_off;        /* samples from dst_base */
+    uint64_t mask_off;       /* EXPLICIT: bytes from mask_base */
+    uint32_t src_stride[2], dst_stride; /* samples */
+    uint32_t mask_stride;    /* EXPLICIT, A64_MASK: bytes */
+    uint8_t  plane[2];
+    uint8_t  w, h;           /* 1, 2, 4 .. 128, independently */
+    uint8_t  kind;           /* SVT_HIP_BLEND_* */
+    uint8_t  mask_src;       /* SVT_HIP_MASK_* */
+    uint8_t  subw, subh;     /* A64_MASK: 0 / 1 */
+    uint8_t  bsize;          /* WEDGE: the BlockSize of the mask; SMOOTH_II: plane_bsize */
+    uint8_t  wedge_index, wedge_sign; /* WEDGE */
+    uint8_t  ii_mode;        /* SMOOTH_II: InterIntraMode 0 .. 3 */
+    uint8_t  pad[4];
+} SvtHipBlendDesc;
+int svt_hip_blend_batch(SvtHipBlendPlanes planes, void *dst_base, const uint8_t *mask_base, const SvtHipBlendDesc *descs, uint32_t n, int bit_depth, uint8_t *status,
+                        void *stream);
+/* Generates the calling thread's device's wedge table now (one launch on `stream` and one synchronisation of it), so that no later call of this section does: a
+ * device-resident caller calls it once per device while it initialises, outside any stream capture.  Returns 0 or SVT_HIP_E_DEVICE. */
+int svt_hip_maskpred_prepare(void *stream);
+/* The masked compound, n blocks of mixed sizes in one launch: what svt_aom_build_masked_compound_no_round (inter_prediction.c:2227) leaves in dst after the two
+ * references were filtered into ConvBufType buffers with the compound roundings of get_conv_params_no_round -- here by the kernel of svt_hip_inter_pred_batch, the first
+ * reference's values staying in registers while the second is filtered.  `p` is a descriptor of svt_hip_inter_pred_batch (both references always used; compound,
+ * fwd_offset, bck_offset ignored; w, h 4 .. 128, the d16 functions' own lower bound).  The combine step is svt_aom_lowbd_blend_a64_d16_mask_c /
+ * svt_aom_highbd_blend_a64_d16_mask_c (blend_a64_mask.c:34, :105) literally: ((m * a + (64 - m) * b) >> 6) - round_offset, ROUND_POWER_OF_TWO(., round_bits), clipped
+ * to the bit depth; the mask per sample with the four (subw, subh) branches of those functions.
+ *   comp_type WEDGE     svt_aom_get_contiguous_soft_mask(wedge_index, wedge_sign, bsize), stride block_size_wide[bsize]; (w << subw, h << subh) within the mask;
+ *   comp_type DIFFWTD   (subw = subh = 0) svt_av1_build_compound_diffwtd_mask_d16_c (C_DEFAULT/inter_prediction_c.c:15) on the two register-held values:
+ *                       clamp(38 + ROUND_POWER_OF_TWO(|a - b|, 2 * FILTER_BITS - round_0 - round_1 + bd - 8) / 16, 0, 64), 64 minus that for mask_type 1
+ *                       (DIFFWTD_38_INV); stored at seg_mask_base + seg_off with stride w, one byte per sample, when seg_mask_base != NULL;
+ *   comp_type EXPLICIT  mask_off, mask_stride into mask_base: how the chroma blocks consume the luma block's seg mask (mask_stride = the luma w, subw / subh = the
+ *                       plane's sub-sampling).
+ * READABLE EXTENT of the references as svt_hip_inter_pred_batch; (w << subw) x (h << subh) of an EXPLICIT mask.  INVALID DESCRIPTORS (those of
+ * svt_hip_inter_pred_batch; w or h below 4; comp_type > 2; subw or subh > 1; WEDGE with a bsize that is not one of the nine, wedge_index > 15, wedge_sign > 1 or a
+ * block larger than the mask; DIFFWTD with mask_type > 1 or a sub-sampling; EXPLICIT without mask_base): status / return value as svt_hip_inter_pred_batch. */
+#define SVT_HIP_COMP_WEDGE    0
+#define SVT_HIP_COMP_DIFFWTD  1
+#define SVT_HIP_COMP_EXPLICIT 2
+typedef struct SvtHipInterPredMaskedDesc {
+    SvtHipInterPredDesc p;
+    uint64_t mask_off;       /* EXPLICIT: bytes from mask_base */
+    uint64_t seg_off;        /* DIFFWTD: bytes from seg_mask_base */
+    uint32_t mask_stride;    /* EXPLICIT */
+    uint8_t  comp_type;      /* SVT_HIP_COMP_* */
+    uint8_t  bsize, wedge_index, wedge_sign; /* WEDGE */
+    uint8_t  mask_type;      /* DIFFWTD: 0 DIFFWTD_38, 1 DIFFWTD_38_INV */
+    uint8_t  subw, subh;
+    uint8_t  pad[5];
+} SvtHipInterPredMaskedDesc;
+int svt_hip_inter_pred_masked_batch(SvtHipInterPredPlanes planes, void *dst_base, const uint8_t *mask_base, uint8_t *seg_mask_base,
+                                    const SvtHipInterPredMaskedDesc *descs, uint32_t n, int bit_depth, uint8_t *status, void *stream);
+/* The wedge / diff-weighted search of n luma blocks: what pick_wedge (fixed_sign 0), pick_wedge_fixed_sign (fixed_sign 1 / 2 = sign 0 / 1) and pick_interinter_seg
+ * (enc_inter_prediction.c:383, :449, :498) compute with use_rate == 0, from the source block and the two predictions as pixel planes.  Per block:
+ *   residual0 = src - p0, residual1 = src - p1, diff10 = p1 - p0 (int16_t); sign_limit = (sum r0^2 - sum r1^2) * 32 in 64 bits;
+ *   ds = clamp(r0^2 - r1^2, INT16_MIN, INT16_MAX) (svt_av1_wedge_compute_delta_squares_c: the saturation is part of the result);
+ *   sign[k] = sum ds * mask(k, 0) > sign_limit (svt_av1_wedge_sign_from_residuals_c, a 64-bit sum), or the fixed sign;
+ *   sse[k] = ROUND_POWER_OF_TWO(sum clamp(64 * r1 + mask(k, sign[k]) * d10, INT16_MIN, INT16_MAX)^2, 12) (svt_av1_wedge_sse_from_residuals_c: the clamp binds at 10 and
+ *   12 bit), a 64-bit sum; sse_diffwtd[t] the same with the DIFFWTD_38 / DIFFWTD_38_INV mask of svt_av1_build_compound_diffwtd_mask_c (bit_depth 8) or _highbd_c with
+ *   its >> (bit_depth - 8) on |p0 - p1| (pick_interinter_seg itself passes EB_TEN_BIT; here the depth is the call's);
+ *   best_wedge_index / best_wedge_sign and best_mask_type by the reference's strict <: the first minimum wins.
+ * With the sixteen sse and sign values a caller can apply the rate model of use_rate == 1 on the host.  bsize is one of the nine wedge sizes.
+ * READABLE EXTENT: block_size_wide x block_size_high[bsize] samples of src, p0 and p1.  INVALID DESCRIPTORS (bsize not one of the nine, fixed_sign > 2, a plane index
+ * >= 32 or without a base): status / return value as svt_hip_inter_pred_batch; the result of an invalid descriptor is not written. */
+typedef struct SvtHipWedgeSearchDesc {
+    uint64_t src_off, p0_off, p1_off;          /* samples from planes.base[*_plane] */
+    uint32_t src_stride, p0_stride, p1_stride; /* samples */
+    uint8_t  src_plane, p0_plane, p1_plane;
+    uint8_t  bsize;
+    uint8_t  fixed_sign;     /* 0: the sign is chosen per wedge index; 1: sign 0 for all; 2: sign 1 for all */
+    uint8_t  pad[7];
+} SvtHipWedgeSearchDesc;
+typedef struct SvtHipWedgeSearchResult {
+    uint64_t sse[16];
+    uint64_t sse_diffwtd[2];
+    uint8_t  sign[16];
+    uint8_t  best_wedge_index, best_wedge_sign, best_mask_type;
+    uint8_t  pad[5];
+} SvtHipWedgeSearchResult;
+int svt_hip_wedge_search_batch(SvtHipBlendPlanes planes, const SvtHipWedgeSearchDesc *descs, uint32_t n, int bit_depth, SvtHipWedgeSearchResult *out, uint8_t *status,
+                               void *stream);
+/* single-call forms with the reference's prototypes: the six pixel-domain blend pointers of common_dsp_rtcd.h:67-78 (exported, NOT installed by svt_hip_setup_rtcd: INTEGRATION.md).
+ * Host pointers; w, h powers of two 1 .. 128 and subx, suby 0 / 1, otherwise nothing is written; dst may be src0 or src1.  The highbd a64_mask form takes its uint16_t
+ * samples through uint8_t pointers, as the reference's does (a plain cast, no CONVERT_TO_SHORTPTR shift: blend_a64_mask.c:252-254). */
+void svt_aom_blend_a64_mask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1, uint32_t src1_stride,
+                                const uint8_t *mask, uint32_t mask_stride, int w, int h, int subx, int suby);
+void svt_aom_highbd_blend_a64_mask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1, uint32_t src1_stride,
+                                       const uint8_t *mask, uint32_t mask_stride, int w, int h, int subx, int suby, int bd);
+void svt_aom_blend_a64_hmask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1, uint32_t src1_stride,
+                                 const uint8_t *mask, int w, int h);
+void svt_aom_blend_a64_vmask_hip(uint8_t *dst, uint32_t dst_stride, const uint8_t *src0, uint32_t src0_stride, const uint8_t *src1, uint32_t src1_stride,
+                                 const uint8_t *mask, int w, int h);
+void svt_aom_highbd_blend_a64_hmask_16bit_hip(uint16_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride, const uint16_t *src1,
+                                              uint32_t src1_stride, const uint8_t *mask, int w, int h, int bd);
+void svt_aom_highbd_blend_a64_vmask_16bit_hip(uint16_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride, const uint16_t *src1,
+                                              uint32_t src1_stride, const uint8_t *mask, int w, int h, int bd);
+/* the two pixel-domain diff-weighted mask builders (common_dsp_rtcd.h:224-227 -> inter_prediction.c:130, :144; mask_type is DIFFWTD_MASK_TYPE, a one-byte enum:
+ * DIFFWTD_38 0, DIFFWTD_38_INV 1; the highbd form takes uint16_t samples through uint8_t pointers and shifts |src0 - src1| by bd - 8) and the four helpers of the
+ * wedge search (common_dsp_rtcd.h:228-229, :1009-1010, aom_dsp_rtcd.h:57-60 -> inter_prediction.c:2330, :2396, enc_inter_prediction.c:338, :375).  Host pointers,
+ * contiguous arrays as in the C.  ACCEPTED RANGE, outside of which nothing is written and the value forms return 0: w, h 1 .. 128, strides >= w, mask_type 0 / 1,
+ * bd 8 / 10 / 12; 1 <= N <= 2^20.  d may be a or b in svt_av1_wedge_compute_delta_squares_hip. */
+void     svt_av1_build_compound_diffwtd_mask_hip(uint8_t *mask, uint8_t mask_type, const uint8_t *src0, int src0_stride, const uint8_t *src1, int src1_stride, int h,
+                                                 int w);
+void     svt_av1_build_compound_diffwtd_mask_highbd_hip(uint8_t *mask, uint8_t mask_type, const uint8_t *src0, int src0_stride, const uint8_t *src1, int src1_stride,
+                                                        int h, int w, int bd);
+uint64_t svt_av1_wedge_sse_from_residuals_hip(const int16_t *r1, const int16_t *d, const uint8_t *m, int N);
+int8_t   svt_av1_wedge_sign_from_residuals_hip(const int16_t *ds, const uint8_t *m, int N, int64_t limit);
+void     svt_av1_wedge_compute_delta_squares_hip(int16_t *d, const int16_t *a, const int16_t *b, int N);
+uint64_t svt_aom_sum_squares_i16_hip(const int16_t *src, uint32_t N);
+
 /* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
 #define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
 #define SVT_HIP_BLOCK_MEAN_PREC_SUB  1
@@ -1253,6 +1397,17 @@ typedef struct SvtHipConvolveParams {
     int32_t   dst_stride, round_0, round_1, plane, is_compound, use_jnt_comp_avg, fwd_offset, bck_offset, use_dist_wtd_comp_avg;
 } SvtHipConvolveParams;
 #endif
+/* the three d16 forms of the masked compound (csrc/maskpred.hip; common_dsp_rtcd.h:103-104, :234-237 -> blend_a64_mask.c:34, :105, C_DEFAULT/inter_prediction_c.c:30).
+ * Host pointers; src0 / src1 are ConvBufType (uint16_t) blocks; round_0 / round_1 are read from conv_params.  ACCEPTED RANGE, outside of which nothing is written: the
+ * roundings as for the jnt_ forms (0 <= round_0 <= 7, 0 <= round_1 <= 7, sum <= 14); w, h powers of two 4 .. 128 and subw, subh 0 / 1 in the blend forms, w, h 1 .. 128
+ * and strides >= w in the builder; mask_type 0 / 1; bd 8 / 10 / 12.  The highbd blend form writes uint16_t samples through its uint8_t pointer, as the reference's. */
+void svt_aom_lowbd_blend_a64_d16_mask_hip(uint8_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride, const uint16_t *src1, uint32_t src1_stride,
+                                          const uint8_t *mask, uint32_t mask_stride, int w, int h, int subw, int subh, SvtHipConvolveParams *conv_params);
+void svt_aom_highbd_blend_a64_d16_mask_hip(uint8_t *dst, uint32_t dst_stride, const uint16_t *src0, uint32_t src0_stride, const uint16_t *src1, uint32_t src1_stride,
+                                           const uint8_t *mask, uint32_t mask_stride, int w, int h, int subx, int suby, SvtHipConvolveParams *conv_params,
+                                           const int bd);
+void svt_av1_build_compound_diffwtd_mask_d16_hip(uint8_t *mask, uint8_t mask_type, const uint16_t *src0, int src0_stride, const uint16_t *src1, int src1_stride, int h,
+                                                 int w, SvtHipConvolveParams *conv_params, int bd);
 /* the sixteen inter-prediction forms (csrc/interpred.hip; described with svt_hip_inter_pred_batch above) */
 #define SVT_HIP_DECLARE_CONVOLVE(name)                                                                                                                               \
     void svt_av1_##name##_hip(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w, int32_t h,                                        \

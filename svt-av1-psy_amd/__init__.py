@@ -318,6 +318,50 @@ for _n in ("lbd", "hbd"):
     PROTOTYPES["svt_cfl_luma_subsampling_420_%s_hip" % _n] = (None, [vp, C.c_int32, vp, C.c_int32, C.c_int32])
 
 
+# AV1 masked prediction (csrc/maskpred.hip): SvtHipBlendPlanes, SvtHipBlendDesc, SvtHipWedgeSearchDesc, SvtHipWedgeSearchResult
+class BlendPlanes(C.Structure):
+    _fields_ = [("base", vp * 32)]
+
+
+BLEND_A64_MASK, BLEND_HMASK, BLEND_VMASK = 0, 1, 2
+MASK_EXPLICIT, MASK_WEDGE, MASK_SMOOTH_II, MASK_OBMC = 0, 1, 2, 3
+BLEND_DESCS_PER_WORKGROUP = 16  # descriptors one workgroup of svt_hip_blend_batch flattens into its tile list
+WEDGE_SEARCH_BLOCKS_PER_WORKGROUP = 4  # blocks (one wave each) of one workgroup of svt_hip_wedge_search_batch
+BlendDesc = np.dtype([("src_off", "<u8", (2,)), ("dst_off", "<u8"), ("mask_off", "<u8"), ("src_stride", "<u4", (2,)), ("dst_stride", "<u4"), ("mask_stride", "<u4"),
+                      ("plane", "u1", (2,)), ("w", "u1"), ("h", "u1"), ("kind", "u1"), ("mask_src", "u1"), ("subw", "u1"), ("subh", "u1"), ("bsize", "u1"),
+                      ("wedge_index", "u1"), ("wedge_sign", "u1"), ("ii_mode", "u1"), ("pad", "u1", (4,))])
+WedgeSearchDesc = np.dtype([("src_off", "<u8"), ("p0_off", "<u8"), ("p1_off", "<u8"), ("src_stride", "<u4"), ("p0_stride", "<u4"), ("p1_stride", "<u4"),
+                            ("src_plane", "u1"), ("p0_plane", "u1"), ("p1_plane", "u1"), ("bsize", "u1"), ("fixed_sign", "u1"), ("pad", "u1", (7,))])
+WedgeSearchResult = np.dtype([("sse", "<u8", (16,)), ("sse_diffwtd", "<u8", (2,)), ("sign", "u1", (16,)), ("best_wedge_index", "u1"), ("best_wedge_sign", "u1"),
+                              ("best_mask_type", "u1"), ("pad", "u1", (5,))])
+assert BlendDesc.itemsize == 64 and WedgeSearchDesc.itemsize == 48 and WedgeSearchResult.itemsize == 168 and C.sizeof(BlendPlanes) == 256
+PROTOTYPES["svt_hip_blend_batch"] = (C.c_int, [BlendPlanes, vp, vp, vp, C.c_uint32, C.c_int, vp, vp])
+PROTOTYPES["svt_hip_wedge_search_batch"] = (C.c_int, [BlendPlanes, vp, C.c_uint32, C.c_int, vp, vp, vp])
+_BL = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp]
+PROTOTYPES["svt_aom_blend_a64_mask_hip"] = (None, _BL + [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int])
+PROTOTYPES["svt_aom_highbd_blend_a64_mask_hip"] = (None, _BL + [C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int])
+for _n in ("hmask", "vmask"):
+    PROTOTYPES["svt_aom_blend_a64_%s_hip" % _n] = (None, _BL + [C.c_int, C.c_int])
+    PROTOTYPES["svt_aom_highbd_blend_a64_%s_16bit_hip" % _n] = (None, _BL + [C.c_int, C.c_int, C.c_int])
+COMP_WEDGE, COMP_DIFFWTD, COMP_EXPLICIT = 0, 1, 2
+InterPredMaskedDesc = np.dtype([("p", InterPredDesc), ("mask_off", "<u8"), ("seg_off", "<u8"), ("mask_stride", "<u4"), ("comp_type", "u1"), ("bsize", "u1"),
+                                ("wedge_index", "u1"), ("wedge_sign", "u1"), ("mask_type", "u1"), ("subw", "u1"), ("subh", "u1"), ("pad", "u1", (5,))])
+assert InterPredMaskedDesc.itemsize == 88
+PROTOTYPES["svt_hip_maskpred_prepare"] = (C.c_int, [vp])
+PROTOTYPES["svt_hip_inter_pred_masked_batch"] = (C.c_int, [InterPredPlanes, vp, vp, vp, vp, C.c_uint32, C.c_int, vp, vp])
+_D16 = [vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, vp, C.c_uint32, C.c_int, C.c_int, C.c_int, C.c_int, vp]
+PROTOTYPES["svt_aom_lowbd_blend_a64_d16_mask_hip"] = (None, _D16)
+PROTOTYPES["svt_aom_highbd_blend_a64_d16_mask_hip"] = (None, _D16 + [C.c_int])
+PROTOTYPES["svt_av1_build_compound_diffwtd_mask_d16_hip"] = (None, [vp, C.c_uint8, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, C.c_int])
+_DW = [vp, C.c_uint8, vp, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+PROTOTYPES["svt_av1_build_compound_diffwtd_mask_hip"] = (None, _DW)
+PROTOTYPES["svt_av1_build_compound_diffwtd_mask_highbd_hip"] = (None, _DW + [C.c_int])
+PROTOTYPES["svt_av1_wedge_sse_from_residuals_hip"] = (C.c_uint64, [vp, vp, vp, C.c_int])
+PROTOTYPES["svt_av1_wedge_sign_from_residuals_hip"] = (C.c_int8, [vp, vp, C.c_int, C.c_int64])
+PROTOTYPES["svt_av1_wedge_compute_delta_squares_hip"] = (None, [vp, vp, vp, C.c_int])
+PROTOTYPES["svt_aom_sum_squares_i16_hip"] = (C.c_uint64, [vp, C.c_uint32])
+
+
 # picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
 BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
 VarBoostFrame = np.dtype([("normalized_base_q_idx", "<i4"), ("min_qindex", "<i4"), ("max_qindex", "<i4"), ("reserved", "<i4")])

@@ -12,11 +12,18 @@
 //    vertical pass as v_dot2_i32_i16 over those pairs; the horizontal sums are v_dot4_i32_i8 on (sample - 128) at 8 bit and v_dot2_i32_i16 at 10 / 12 bit.
 //  * compound: both references are filtered by the same wave, the first one's ConvBufType values stay in eight registers per lane; the intermediate buffer of the
 //    reference's two calls never reaches memory.
+//  * masked compound (COMPOUND_WEDGE / COMPOUND_DIFFWTD): a third template parameter; the same two passes, then the d16 blend on the two register-held values with a wedge,
+//    explicit or diff-weighted mask.  The unmasked instantiations compile to what they compiled to before it existed.
 //  * no global atomics, nothing to zero beforehand, every output sample is written exactly once by plain stores: results do not depend on launch order.
 #include "svt_hip_common.h"
 #include "../../include/svtav1_hip.h"
+#include "maskpred_tables.h"
+#include <type_traits>
+
+namespace svthip { const uint8_t* wedge_table(hipStream_t st); } // maskpred.hip: the device's 100 352-byte wedge table, generated at first use
 
 namespace {
+using namespace svt_maskpred; // kBw, kBh, kSlotOff, wedge_slot: the wedge table's layout
 
 constexpr int DPW     = 16;           // descriptors per workgroup group
 constexpr int TPB     = 256;          // threads per workgroup
@@ -99,6 +106,10 @@ struct Aux {
     int32_t   force_case; // single-call forms: the case (bit 0: x filtered, bit 1: y filtered); the batched entry takes it from the phases
     int32_t   bd, r0, r1_single, r1_compound;
     Taps      tx, ty;    // single-call forms: the caller's taps
+    // the masked instantiation only (last, so that the other instantiations' argument loads stay where they were)
+    const uint8_t* wedge;     // the wedge table of maskpred.hip
+    const uint8_t* mask_base; // EXPLICIT masks
+    uint8_t*       seg_base;  // DIFFWTD: where the mask is stored, or NULL
 };
 
 __host__ __device__ __forceinline__ bool dim_ok(const uint32_t v) { return v >= 2 && v <= 128 && (v & (v - 1)) == 0; }
@@ -110,6 +121,19 @@ __host__ __device__ __forceinline__ bool desc_ok(const SvtHipInterPredDesc& d, c
         if (d.subpel_x[k] > 15 || d.subpel_y[k] > 15 || d.plane[k] >= 32 || planes.base[d.plane[k]] == nullptr) return false;
     return true;
 }
+__device__ __forceinline__ bool desc_ok(const SvtHipInterPredMaskedDesc& m, const SvtHipInterPredPlanes& planes, const uint8_t* mask_base) {
+    SvtHipInterPredDesc d = m.p;
+    d.compound            = 1; // always two references
+    if (!desc_ok(d, planes) || d.w < 4 || d.h < 4 || m.comp_type > SVT_HIP_COMP_EXPLICIT || m.subw > 1 || m.subh > 1) return false; // (the d16 functions' lower bound)
+    if (m.comp_type == SVT_HIP_COMP_WEDGE)
+        return wedge_slot(m.bsize) >= 0 && m.wedge_index <= 15 && m.wedge_sign <= 1 && ((uint32_t)d.w << m.subw) <= kBw[m.bsize] && ((uint32_t)d.h << m.subh) <= kBh[m.bsize];
+    if (m.comp_type == SVT_HIP_COMP_DIFFWTD) return m.mask_type <= 1 && m.subw == 0 && m.subh == 0;
+    return mask_base != nullptr;
+}
+__device__ __forceinline__ const SvtHipInterPredDesc& desc_base(const SvtHipInterPredDesc& d) { return d; }
+__device__ __forceinline__ const SvtHipInterPredDesc& desc_base(const SvtHipInterPredMaskedDesc& d) { return d.p; }
+__device__ __forceinline__ int load_byte(const uint8_t* p) { return (int)*(const SVT_HIP_GLOBAL_AS uint8_t*)p; }
+
 // The tiling of a w x h block, the ONE place that knows it: tiles of 2^lw = min(w, 32) columns by th = min(h, 512 >> lw) rows, ntx across and nty down.  The prefix
 // sum counts ntx * nty tiles and the tile loop lays them out with the same three numbers (a 64x8 block is two 32x8 tiles, not 64 * 8 / 512 = one).
 struct Tiling { int lw, th; uint32_t ntx, nty; };
@@ -245,9 +269,14 @@ __device__ __forceinline__ void reference_pass(int (&v)[NPL], const PIX* __restr
 
 // FORM = false: the batched entry (AV1's tables, the roundings of get_conv_params_no_round, the case follows the phases); FORM = true: one block of a single-call form
 // (the caller's taps and roundings, the case its name stands for, aux.mode).
-template <typename PIX, bool FORM>
-__global__ __launch_bounds__(TPB) void inter_pred_kernel(const SvtHipInterPredPlanes planes, PIX* __restrict__ dst_base, const SvtHipInterPredDesc* __restrict__ descs,
+// MASKED: the masked compound of svt_aom_build_masked_compound_no_round (inter_prediction.c:2227): descriptors are SvtHipInterPredMaskedDesc, both references are
+// always filtered, and the last step is svt_aom_lowbd_ / highbd_blend_a64_d16_mask_c (blend_a64_mask.c:34, :105) on the two ConvBufType values, the mask a wedge, bytes
+// of aux.mask_base, or svt_av1_build_compound_diffwtd_mask_d16_c (C_DEFAULT/inter_prediction_c.c:15) on those same two values.
+template <typename PIX, bool FORM, bool MASKED = false>
+__global__ __launch_bounds__(TPB) void inter_pred_kernel(const SvtHipInterPredPlanes planes, PIX* __restrict__ dst_base,
+                                                         const std::conditional_t<MASKED, SvtHipInterPredMaskedDesc, SvtHipInterPredDesc>* __restrict__ descs,
                                                          const uint32_t n, uint8_t* __restrict__ status, const Aux aux) {
+    typedef std::conditional_t<MASKED, SvtHipInterPredMaskedDesc, SvtHipInterPredDesc> DESC;
     __shared__ uint32_t pre[DPW + 1];         // exclusive prefix sum of the tile counts
     __shared__ uint32_t im[WAVES][IM_DW];     // the waves' intermediate slices
     const int      tid = threadIdx.x, l = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -255,9 +284,11 @@ __global__ __launch_bounds__(TPB) void inter_pred_kernel(const SvtHipInterPredPl
     if (tid < 64) { // (the first wave, whole: the scan's shuffles are wave-uniform)
         uint32_t cnt = 0;
         if (tid < DPW && first + tid < n) {
-            const SvtHipInterPredDesc d  = descs[first + tid];
-            const bool                ok = desc_ok(d, planes);
-            if (ok) cnt = tile_count(d.w, d.h);
+            const DESC dd = descs[first + tid];
+            bool       ok;
+            if constexpr (MASKED) ok = desc_ok(dd, planes, aux.mask_base);
+            else ok = desc_ok(dd, planes);
+            if (ok) cnt = tile_count(desc_base(dd).w, desc_base(dd).h);
             if (status && blockIdx.y == 0) status[first + tid] = ok ? 0 : 1;
         }
         uint32_t inc = cnt;
@@ -278,7 +309,8 @@ __global__ __launch_bounds__(TPB) void inter_pred_kernel(const SvtHipInterPredPl
         for (int s = DPW >> 1; s >= 1; s >>= 1)
             if (pre[di + s] <= u) di += s;
         di = __builtin_amdgcn_readfirstlane(di); // the descriptor, and every branch taken on it, is the wave's: scalar loads, scalar branches
-        const SvtHipInterPredDesc d = descs[first + di];
+        const DESC                 dm = descs[first + di];
+        const SvtHipInterPredDesc& d  = desc_base(dm);
         const int      w = d.w, h = d.h;
         const Tiling   tl = tiling_of((uint32_t)w, (uint32_t)h);
         const int      lw = tl.lw, tw = 1 << lw, th = tl.th, npx = th << lw;
@@ -286,12 +318,26 @@ __global__ __launch_bounds__(TPB) void inter_pred_kernel(const SvtHipInterPredPl
         const bool     on = l < npx;
         const uint32_t loc = u - pre[di], ntx = tl.ntx, tyi = loc / ntx, txi = loc - tyi * ntx;
         const uint32_t x0 = txi << lw, y0 = tyi * (uint32_t)th;
-        const bool     compound = FORM ? aux.mode != 0 : d.compound != 0;
+        const bool     compound = MASKED ? true : (FORM ? aux.mode != 0 : d.compound != 0);
         const int      r1 = compound ? aux.r1_compound : aux.r1_single;
-        const int      npass = !FORM && d.compound != 0 ? 2 : 1;
+        const int      npass = MASKED ? 2 : (!FORM && d.compound != 0 ? 2 : 1);
         const int      ob = bd + 14 - r0, ro = (1 << (ob - r1)) + (1 << (ob - r1 - 1)), rb = 14 - r0 - r1;
         PIX*           out = dst_base + d.dst_off + (size_t)y0 * d.dst_stride + x0;
         int            a[NPL] = {}; // the first reference's ConvBufType values
+        const uint8_t* mp = nullptr; // MASKED, WEDGE / EXPLICIT: the mask's bytes, its stride and sub-sampling
+        uint32_t       ms = 0;
+        int            subw = 0, subh = 0, ctype = 0, inv = 0;
+        uint64_t       seg_off = 0;
+        if constexpr (MASKED) {
+            ctype = dm.comp_type, subw = dm.subw, subh = dm.subh, inv = dm.mask_type, seg_off = dm.seg_off;
+            if (ctype == SVT_HIP_COMP_WEDGE) {
+                ms = kBw[dm.bsize];
+                mp = aux.wedge + kSlotOff[wedge_slot(dm.bsize)] + (uint32_t)(dm.wedge_index * 2 + dm.wedge_sign) * ms * kBh[dm.bsize];
+            } else if (ctype == SVT_HIP_COMP_EXPLICIT) {
+                ms = dm.mask_stride;
+                mp = aux.mask_base + dm.mask_off;
+            }
+        }
         for (int pass = 0; pass < npass; pass++) {
             const int      sx = pass ? d.subpel_x[1] : d.subpel_x[0], sy = pass ? d.subpel_y[1] : d.subpel_y[0];
             const uint32_t stride = pass ? d.src_stride[1] : d.src_stride[0];
@@ -322,7 +368,24 @@ __global__ __launch_bounds__(TPB) void inter_pred_kernel(const SvtHipInterPredPl
                     const int i = l + 64 * j;
                     if (j < nj && on) {
                         int tmp = FORM ? (int)aux.cb[(size_t)(y0 + (i >> lw)) * aux.cb_stride + x0 + (i & (tw - 1))] : a[j];
-                        if (d.compound == 2) tmp = (tmp * (int)d.fwd_offset + v[j] * (int)d.bck_offset) >> 4; // DIST_PRECISION_BITS
+                        if constexpr (MASKED) {
+                            const int      bq = (int)(uint16_t)v[j]; // the second reference as the reference stores it: ConvBufType
+                            const uint32_t x = x0 + (uint32_t)(i & (tw - 1)), y = y0 + (uint32_t)(i >> lw);
+                            int            m;
+                            if (ctype == SVT_HIP_COMP_DIFFWTD) { // diffwtd_mask_d16: round = 2 * FILTER_BITS - round_0 - round_1 + (bd - 8)
+                                m = 38 + (rpot(tmp > bq ? tmp - bq : bq - tmp, rb + bd - 8) >> 4); // DIFF_FACTOR 16
+                                m = m > 64 ? 64 : m;
+                                if (inv) m = 64 - m;
+                                if (aux.seg_base) aux.seg_base[seg_off + (size_t)y * (uint32_t)w + x] = (uint8_t)m; // stride w, as the C writes it
+                            } else {
+                                const uint8_t* q = mp + ((size_t)(y << subh) * ms + (x << subw));
+                                m                = load_byte(q);
+                                if (subw && subh) m = (m + load_byte(q + ms) + load_byte(q + 1) + load_byte(q + ms + 1) + 2) >> 2;
+                                else if (subw) m = (m + load_byte(q + 1) + 1) >> 1; // AOM_BLEND_AVG
+                                else if (subh) m = (m + load_byte(q + ms) + 1) >> 1;
+                            }
+                            tmp = (m * tmp + (64 - m) * bq) >> 6; // a plain shift: the rounding comes once, below (blend_a64_mask.c:23-29)
+                        } else if (d.compound == 2) tmp = (tmp * (int)d.fwd_offset + v[j] * (int)d.bck_offset) >> 4; // DIST_PRECISION_BITS
                         else tmp = (tmp + v[j]) >> 1;
                         tmp                 = rpot(tmp - ro, rb);
                         out[(size_t)(i >> lw) * d.dst_stride + (i & (tw - 1))] = (PIX)(tmp < 0 ? 0 : (tmp > maxv ? maxv : tmp));
@@ -338,6 +401,13 @@ __global__ __launch_bounds__(TPB) void inter_pred_check_kernel(const SvtHipInter
                                                                uint32_t* __restrict__ bad_out) {
     bool bad = false;
     for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) bad |= !desc_ok(descs[i], planes);
+    if (bad) *bad_out = 1;
+}
+
+__global__ __launch_bounds__(TPB) void inter_pred_masked_check_kernel(const SvtHipInterPredPlanes planes, const uint8_t* mask_base,
+                                                                      const SvtHipInterPredMaskedDesc* __restrict__ descs, const uint32_t n, uint32_t* __restrict__ bad_out) {
+    bool bad = false;
+    for (uint32_t i = blockIdx.x * TPB + threadIdx.x; i < n; i += gridDim.x * TPB) bad |= !desc_ok(descs[i], planes, mask_base);
     if (bad) *bad_out = 1;
 }
 
@@ -438,6 +508,39 @@ int svt_hip_inter_pred_batch(SvtHipInterPredPlanes planes, void* dst_base, const
         if (*(volatile uint32_t*)bad) return -1;
     }
     launch<false>(planes, dst_base, descs, n, status, batch_aux(bit_depth), st);
+    SVT_HIP_ENTRY_CATCH(SVT_HIP_E_DEVICE)
+    return 0;
+}
+
+int svt_hip_inter_pred_masked_batch(SvtHipInterPredPlanes planes, void* dst_base, const uint8_t* mask_base, uint8_t* seg_mask_base,
+                                    const SvtHipInterPredMaskedDesc* descs, uint32_t n, int bit_depth, uint8_t* status, void* stream) {
+    if (bit_depth != 8 && bit_depth != 10 && bit_depth != 12) return -1;
+    if (n == 0) return 0;
+    if (!dst_base || !descs) return -1;
+    if (svthip::failed()) return SVT_HIP_E_DEVICE;
+    SVT_HIP_ENTRY_TRY
+    svthip::ensure_device();
+    hipStream_t st  = (hipStream_t)stream;
+    Aux         aux = batch_aux(bit_depth);
+    aux.wedge       = svthip::wedge_table(st);
+    aux.mask_base   = mask_base;
+    aux.seg_base    = seg_mask_base;
+    if (!status) {
+        svthip::HostCall& c = svthip::host_call();
+        c.begin_small();
+        c.reserve(0, 256);
+        uint32_t* bad = (uint32_t*)c.palloc(64);
+        *bad          = 0;
+        hipLaunchKernelGGL(inter_pred_masked_check_kernel, dim3(n < 1024u * TPB ? (n + TPB - 1) / TPB : 1024u), dim3(TPB), 0, st, planes, mask_base, descs, n, bad);
+        SVT_LAUNCH_CHECK();
+        HIP_CHECK(hipStreamSynchronize(st));
+        if (*(volatile uint32_t*)bad) return -1;
+    }
+    const dim3 grid((n + DPW - 1) / DPW, SPLIT), block(TPB);
+    if (bit_depth > 8)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(inter_pred_kernel<uint16_t, false, true>), grid, block, 0, st, planes, (uint16_t*)dst_base, descs, n, status, aux);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(inter_pred_kernel<uint8_t, false, true>), grid, block, 0, st, planes, (uint8_t*)dst_base, descs, n, status, aux);
+    SVT_LAUNCH_CHECK();
     SVT_HIP_ENTRY_CATCH(SVT_HIP_E_DEVICE)
     return 0;
 }
