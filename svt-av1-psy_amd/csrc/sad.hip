@@ -531,44 +531,76 @@ __device__ __forceinline__ uint32_t dpp_min_quad_xor2(uint32_t v) { return umin3
 __device__ __forceinline__ uint32_t dpp_min_row_ror4(uint32_t v) { return umin32(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x124, 0xf, 0xf, false)); }
 __device__ __forceinline__ uint32_t dpp_min_row_ror8(uint32_t v) { return umin32(v, (uint32_t)__builtin_amdgcn_update_dpp(-1, (int)v, 0x128, 0xf, 0xf, false)); }
 
-// The window of one item, staged by its own wave: rows x width bytes (64 <= width < 16 * (NF + 1), any global alignment / stride) into LDS rows of PITCH dwords.
-// NF = full 16-byte chunks per row.  Lane -> (row within a block of RPI = 64 / NF rows, chunk) once; every further chunk of the lane lies RPI rows lower, so the walk
-// is a scalar step on the row base and a compile-time LDS offset: no per-chunk row / column arithmetic, no funnel shift, no zeroing (stage_rows_wide_step pays ~50 VALU
-// per chunk for the general case).  Four loads per lane are in flight before the first LDS store.  The partial chunk of a row (width % 16 bytes) is a pass of its own
-// over the rows: the 16 bytes that END at the row end, shifted down by a wave-uniform byte count and zero filled; its loads are issued first of all.
+// ME_SCALARS_HERE(x, ...) wants the wave-uniform values it names in scalar registers at this point of the program: the scalar loads that feed them are issued together
+// and waited for once, where the compiler would fetch each value in the block that first needs it (one memory round trip per block).  x is handed back as a value
+// the compiler knows nothing more about, which is what ties the statement to the program (it is neither volatile nor a memory access, so the loads behind it stay
+// scalar loads); the emulator build has no such registers.
+#ifdef SVT_HIP_EMU
+#define ME_SCALARS_HERE(x, ...) ((void)0)
+#else
+#define ME_SCALARS_HERE(x, ...) asm("" : "+s"(x) : __VA_ARGS__)
+#endif
+// A load of T (dwords, any byte alignment) at a wave-uniform global address plus a 32-bit lane offset, as the instruction has it: scalar base, one VGPR of offset.
+// The base is handed through an empty asm statement as an integer in scalar registers, or the compiler folds the lane offset into it first and walks 64-bit lane
+// addresses from row to row (eight v_lshl_add_u64 for the source block); as a pointer it would come back without its address space and load through flat_load.
+template <typename T>
+__device__ __forceinline__ T me_load_at(const uint8_t* base, const uint32_t lane_off) {
+#ifdef SVT_HIP_EMU
+    return *(const T*)(base + lane_off);
+#else
+    typedef uint32_t __attribute__((ext_vector_type(sizeof(T) / 4))) vec_t;
+    typedef vec_t __attribute__((aligned(1))) vec_a1_t;
+    static_assert(sizeof(T) == sizeof(vec_t), "dwords");
+    uintptr_t b = (uintptr_t)base;
+    asm("" : "+s"(b));
+    const vec_t x = *(const __attribute__((address_space(1))) vec_a1_t*)(b + (uintptr_t)lane_off);
+    T           t;
+    __builtin_memcpy(&t, &x, sizeof(T));
+    return t;
+#endif
+}
+
+// The window of one item, staged by its own wave: rows x width bytes (64 <= width < 16 * (NF + 1), 64 <= rows <= 79, any global alignment / stride) into LDS rows of
+// PITCH dwords.  NF = full 16-byte chunks per row.  Lane -> (row within a pass of RPI = 64 / NF rows, chunk) once; every further chunk of the lane lies RPI rows lower.
+// EVERY load of the window is issued in straight-line code before the first wait: the two loads of the partial chunk (width % 16 bytes: the 16 bytes that END at the
+// row end, shifted down by a wave-uniform byte count and zero filled), then NP passes of one unaligned dwordx4 per lane (5 with NF = 4, 7 with NF = 5: the most rows a
+// window has; the compiler orders the loads among themselves), and the LDS stores follow behind descending vmcnt counts.  No load sits under a branch (under exec-masked branches in a loop the compiler waited for
+// every load before it issued the next): a lane whose row lies below the window takes the window's LAST row instead, so it reloads a chunk inside the window, and
+// its store lands on the same LDS address with the same bytes as the store of the lane that owns the row -- the duplicates are left to land, nothing is predicated.
+// The first 64 / RPI passes need no clamp (every window has 64 rows): scalar step on the row base, compile-time LDS offset.  With NF = 5 lanes 60-63 have no chunk of
+// their own and repeat lanes 55-58.  A window without a partial chunk (width 64 or 80) still issues the two tail loads (they re-read the last 16 bytes of a row) and
+// skips what follows them.
 // Same contract as stage_rows_u8: nothing outside [row, row + width) is read; every chunk that holds window bytes is written whole, zero filled behind the row end.
+constexpr int ME_WAVE_MAX_ROWS = 64 + (int)ME_WAVE_MAX_H - 1;
 template <int NF, int PITCH>
 __device__ __forceinline__ void stage_window_wave(uint32_t* lds, const uint8_t* g, const uint32_t gstride, const int width, const int rows, const int l) {
-    constexpr int RPI = 64 / NF;
-    const int     rem = width & 15, back = 16 - rem; // bytes of the partial chunk; rows <= 128: two of them per lane at most
-    const bool    p0 = rem != 0 && l < rows, p1 = rem != 0 && l + 64 < rows;
-    u32x4_a1      t[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
-    const uint32_t tail_off = (uint32_t)l * gstride + (uint32_t)(width - 16);
-    if (p0) t[0] = *(const u32x4_a1*)(g + tail_off);
-    if (p1) t[1] = *(const u32x4_a1*)(g + (size_t)64 * gstride + tail_off);
+    constexpr int RPI = 64 / NF;                            // rows per pass
+    constexpr int NP  = (ME_WAVE_MAX_ROWS + RPI - 1) / RPI; // passes of the tallest window
+    constexpr int NPF = 64 / RPI;                           // passes every window has in full
+    const int      rem = width & 15, back = 16 - rem;       // bytes of the partial chunk; 64 <= rows < 128: two of them per lane at most
+    const uint32_t last = (uint32_t)(rows - 1);
+    const uint32_t tr1  = umin32((uint32_t)l + 64u, last);  // the lane's second row of the partial-chunk pass
+    u32x4_a1       t[2], v[NP];
+    t[0] = me_load_at<u32x4_a1>(g, (uint32_t)l * gstride + (uint32_t)(width - 16));
+    t[1] = me_load_at<u32x4_a1>(g, tr1 * gstride + (uint32_t)(width - 16));
 
-    const int lr = l / NF, lc = l - lr * NF;
-    if (lr < RPI) { // (NF = 5: lanes 60-63 have no chunk)
-        const uint32_t goff = (uint32_t)lr * gstride + (uint32_t)lc * 16u;
-        uint32_t*      lp   = lds + lr * PITCH + lc * 4;
-        for (int r0 = 0; r0 < rows; r0 += 4 * RPI) {
-            const uint8_t* gb = g + (size_t)r0 * gstride; // wave-uniform row base
-            u32x4_a1       v[4];
+    const int      le = (NF * RPI < 64 && l >= NF * RPI) ? l - NF : l;
+    const int      lr = le / NF, lc = le - lr * NF;
+    const uint32_t goff = (uint32_t)lr * gstride + (uint32_t)lc * 16u;
+    uint32_t*      lp   = lds + lr * PITCH + lc * 4;
+    uint32_t       rk[NP];
 #pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (r0 + k * RPI + lr < rows) v[k] = *(const u32x4_a1*)(gb + (size_t)(k * RPI) * gstride + goff);
-#pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (r0 + k * RPI + lr < rows) {
-                    uint32_t* o = lp + (r0 + k * RPI) * PITCH;
-                    *(u32x2_a8*)(o + 0) = u32x2_a8{v[k].x, v[k].y};
-                    *(u32x2_a8*)(o + 2) = u32x2_a8{v[k].z, v[k].w};
-                }
+    for (int k = 0; k < NP; k++) {
+        if (k < NPF) {
+            v[k] = me_load_at<u32x4_a1>(g + (size_t)(k * RPI) * gstride, goff);
+        } else {
+            rk[k] = umin32((uint32_t)(lr + k * RPI), last);
+            v[k]  = me_load_at<u32x4_a1>(g, rk[k] * gstride + (uint32_t)lc * 16u);
         }
     }
+    if (rem != 0) { // wave-uniform
 #pragma unroll
-    for (int k = 0; k < 2; k++)
-        if (k == 0 ? p0 : p1) {
+        for (int k = 0; k < 2; k++) {
             uint32_t x0 = t[k].x, x1 = t[k].y, x2 = t[k].z, x3 = t[k].w; // shift the 128-bit value right by `back` bytes, zero fill
             if (back & 4) { x0 = x1; x1 = x2; x2 = x3; x3 = 0; }
             if (back & 8) { x0 = x2; x1 = x3; x2 = 0; x3 = 0; }
@@ -577,11 +609,21 @@ __device__ __forceinline__ void stage_window_wave(uint32_t* lds, const uint8_t* 
             x1 = __builtin_amdgcn_alignbyte(x2, x1, bs);
             x2 = __builtin_amdgcn_alignbyte(x3, x2, bs);
             x3 = __builtin_amdgcn_alignbyte(0u, x3, bs);
-            uint32_t* o = lds + (l + 64 * k) * PITCH + NF * 4;
+            uint32_t* o = lds + (k == 0 ? (uint32_t)l : tr1) * PITCH + NF * 4;
             if (NF * 4 + 0 < PITCH) *(u32x2_a8*)(o + 0) = u32x2_a8{x0, x1};
             if (NF * 4 + 2 < PITCH) *(u32x2_a8*)(o + 2) = u32x2_a8{x2, x3};
         }
+    }
+#pragma unroll
+    for (int k = 0; k < NP; k++) {
+        uint32_t* o = k < NPF ? lp + (k * RPI) * PITCH : lds + rk[k] * PITCH + lc * 4;
+        *(u32x2_a8*)(o + 0) = u32x2_a8{v[k].x, v[k].y};
+        *(u32x2_a8*)(o + 2) = u32x2_a8{v[k].z, v[k].w};
+    }
 }
+
+struct __attribute__((aligned(8))) MeDescWords { uint32_t w[8]; }; // an SvtHipMeSearchDesc as the eight dwords of ONE scalar load
+static_assert(sizeof(SvtHipMeSearchDesc) == 32, "descriptor layout");
 
 template <bool SUB, int PITCH>
 __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __restrict__ src_base, const uint8_t* __restrict__ ref_base,
@@ -589,10 +631,17 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
                                                               uint32_t* __restrict__ best_sad, uint32_t* __restrict__ best_mv) {
     HIP_DYNAMIC_SHARED(uint32_t, smem)
     const int      l    = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    // two scalar round trips in front of the first vector load: every kernel argument in one batch, then the 32 bytes of the descriptor as one load
+    uint32_t nn = n;
+    ME_SCALARS_HERE(nn, "s"(src_base), "s"(ref_base), "s"(descs), "s"(win_dw), "s"(best_sad), "s"(best_mv));
     const uint32_t item = xcd_remap(blockIdx.x, gridDim.x) * 4 + (uint32_t)wv; // four consecutive items (neighbouring SBs of one reference) per workgroup
-    if (item >= n) return;
-    const SvtHipMeSearchDesc d = descs[item];
-    const int    W = d.search_area_width, H = d.search_area_height;
+    if (item >= nn) return;
+    MeDescWords dw = *(const MeDescWords*)(descs + item);
+    ME_SCALARS_HERE(dw.w[7], "s"(dw.w[0]), "s"(dw.w[1]), "s"(dw.w[2]), "s"(dw.w[3]), "s"(dw.w[4]), "s"(dw.w[5]), "s"(dw.w[6]));
+    const size_t   src_off = (size_t)dw.w[0] | ((size_t)dw.w[1] << 32), ref_off = (size_t)dw.w[2] | ((size_t)dw.w[3] << 32);
+    const uint32_t src_stride = dw.w[4], ref_stride = dw.w[5];
+    const int      xo = (int16_t)(dw.w[6] & 0xffffu), yo = (int16_t)(dw.w[6] >> 16);
+    const int      W = (int)(dw.w[7] & 0xffffu), H = (int)(dw.w[7] >> 16);
     const size_t o = (size_t)item * SVT_HIP_ME_NUM_BLOCKS;
     if (W <= 0 || H <= 0) { // an empty search area reports "nothing found"
         for (int k = l; k < SVT_HIP_ME_NUM_BLOCKS; k += 64) { best_sad[o + k] = MAX_SAD_VALUE; best_mv[o + k] = 0; }
@@ -602,18 +651,19 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
     const int bx = (l & 1) | ((l >> 1) & 2) | ((l >> 2) & 4);
     const int by = ((l >> 1) & 1) | ((l >> 2) & 2) | ((l >> 3) & 4);
     uint32_t  s[8][2];
-    {
-        const uint8_t* sp = src_base + d.src_off + (size_t)(by * 8) * d.src_stride + bx * 8;
+    { // the lane's 8x8 source block: scalar row bases and one 32-bit lane offset; issued in front of the window loads, first needed at the first qsad
+        const uint8_t* sp  = src_base + src_off;
+        const uint32_t slo = (uint32_t)(by * 8) * src_stride + (uint32_t)(bx * 8);
 #pragma unroll
         for (int r = 0; r < 8; r++) {
-            const u32x2_a1 t = *(const u32x2_a1*)(sp + (size_t)r * d.src_stride);
+            const u32x2_a1 t = me_load_at<u32x2_a1>(sp + (size_t)r * src_stride, slo);
             s[r][0] = t.x; s[r][1] = t.y;
         }
     }
     const int width = 64 + W - 1;
     // 64 <= width <= 87: four full 16-byte chunks per row, five from W = 17 on (never with the 18-dword pitch of the areas up to 8 wide)
-    if (PITCH >= 22 && (width >> 4) == 5) stage_window_wave<5, PITCH>(win, ref_base + d.ref_off, d.ref_stride, width, 64 + H - 1, l);
-    else stage_window_wave<4, PITCH>(win, ref_base + d.ref_off, d.ref_stride, width, 64 + H - 1, l);
+    if (PITCH >= 22 && (width >> 4) == 5) stage_window_wave<5, PITCH>(win, ref_base + ref_off, ref_stride, width, 64 + H - 1, l);
+    else stage_window_wave<4, PITCH>(win, ref_base + ref_off, ref_stride, width, 64 + H - 1, l);
     __builtin_amdgcn_wave_barrier(); // the slice belongs to this wave alone: LDS program order is enough on the hardware
 
     uint32_t best8 = 0xffffffffu, best16 = 0xffffffffu, best32 = 0xffffffffu, best64 = 0xffffffffu;
@@ -629,7 +679,6 @@ __global__ __launch_bounds__(256) void me_fullpel_wave_kernel(const uint8_t* __r
         const auto x32 = __builtin_amdgcn_permlane32_swap(best64, best64, false, false);
         best64         = umin32(x32[0], x32[1]);
     }
-    const int xo = d.x_search_area_origin, yo = d.y_search_area_origin;
     auto emit = [&](const int idx, const uint32_t key, const bool is8) {
         const uint32_t sad = is8 ? (key >> 16) : (key >> KEY_POS_BITS);
         const int      X = (int)(key & 63u), Y = (int)((key >> 6) & 31u);

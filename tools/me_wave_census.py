@@ -8,6 +8,9 @@ Compiles sad.hip for gfx950 with the flags of csrc/Makefile plus `-S --cuda-devi
   set-up + staging : everything before the first ring prologue (the block that issues the 14 ds_read2 of rows 0-6): descriptor, the lane's source block,
                      stage_window_wave.  Its loop (a branch back to an earlier label) is the four-chunks-in-flight loop, ceil(rows / (4 * (64 / NF))) trips;
                      the figure is the heaviest forward path through the region, an upper bound (the staging is instantiated per NF, one instance runs).
+  start of a wave  : three figures of the latency a wave meets before and inside its search (start_figures below): the window loads a path of the set-up issues
+                     before its first `s_waitcnt vmcnt`, the scalar waits (kernel arguments, descriptor) in front of the first vector load, and per step block the
+                     qsads between the read of the new ring row and the first qsad that takes it.
   search instance  : one per instantiation of me_search_strips (FULL = W % 4 == 0, and the general one); an instance starts at a ring prologue.
                        prologue : per x group, the blocks without a v_qsad_pk_u16_u8 or a v_permlane32_swap
                        step     : a block with 16 (sub_sad: 8) qsad = one y step; its tail = VALU - qsad
@@ -107,6 +110,62 @@ def blocks_of(lines, name):
     return out
 
 
+def start_figures(bl, idx, n_pre):
+    """The start of a wave, from the set-up blocks bl[:n_pre] (forward paths only) and the step blocks:
+      window loads before the first vmcnt wait : 16-byte (or 12 + 4) vector loads a path issues before its first `s_waitcnt vmcnt`, [min, max] over the paths
+      scalar waits before the first vector load: `s_waitcnt lgkmcnt` with a scalar load outstanding, on the path from the entry to the first global load (max over paths)
+      qsads between ring-row read and first use: per step block, the qsads issued between the last ds_read2_b32 pair of the ring row and the first qsad that takes its
+                                                 register; where the step that reads the row does not use it (sub_sad), the qsads left in the block, marked '+'."""
+    def succ(i):
+        b = bl[i]
+        nxt = [idx[t] for t in b["to"] if t in idx and idx[t] > i]
+        if b["ops"][-1] != "s_branch":
+            nxt.append(i + 1)
+        return [j for j in nxt if j < n_pre]
+
+    loads, waits = [], []
+
+    def walk(i, nload, pend, nwait, seen_vec, done_l):
+        for t in bl[i]["txt"]:
+            op = t.split()[0]
+            if op.startswith("s_load"):
+                pend = True
+            elif op == "s_waitcnt":
+                if "lgkmcnt" in t and pend and not seen_vec:
+                    nwait, pend = nwait + 1, False
+                if "vmcnt" in t and not done_l:
+                    loads.append(nload)
+                    done_l = True
+            elif op.startswith(("global_load", "flat_load")):
+                if not seen_vec:
+                    waits.append(nwait)
+                    seen_vec = True
+                if op.endswith(("dwordx4", "dwordx3")) and not done_l:
+                    nload += 1
+        if done_l and seen_vec:
+            return
+        nx = succ(i)
+        if not nx and not done_l and nload:
+            loads.append(nload)
+        for j in nx:
+            walk(j, nload, pend, nwait, seen_vec, done_l)
+    walk(0, 0, False, 0, False, False)
+    loads = [n for n in loads if n]  # (a path that waits without a window load behind it is the exit of an empty area or of a wave past n)
+    dist = []
+    for b in bl:
+        if not b["qsad"] or b["qsad"] < 8:
+            continue
+        reads = [(k, re.match(r"ds_read2_b32 (v\[\d+:\d+\])", t).group(1)) for k, t in enumerate(b["txt"]) if t.startswith("ds_read2_b32")]
+        if not reads:
+            dist.append("none in the block")
+            continue
+        k0, reg = reads[0]
+        after = [t for t in b["txt"][k0:] if t.startswith("v_qsad_pk_u16_u8")]
+        use = next((n for n, t in enumerate(after) if re.match(r"v_qsad_pk_u16_u8 \S+ %s," % re.escape(reg), t)), None)
+        dist.append(str(use) if use is not None else "%d+" % len(after))
+    return loads, waits, dist
+
+
 def metadata(lines, name):
     text = "\n".join(lines)
     sym = re.search(r"\.name:\s+(_Z\w*%s\w*)" % re.escape(name), text).group(1)
@@ -169,6 +228,11 @@ def main():
     chunks = (64 + H - 1) * ((64 + W - 1 + 15) >> 4)
     print("set-up + staging : static %4d, executed at %dx%d <= %4d (chunk loop x %d; %d chunks of 16 bytes, source block and descriptor included)" %
           (st_static, W, H, st_exec, trips, chunks))
+
+    wl, sw, dist = start_figures(bl, idx, len(pre))
+    print("start of a wave  : window loads issued before the first vmcnt wait %s over the paths of the set-up; scalar waits before the first vector load %s; "
+          "qsads between a step's ring-row read and its first use %s" %
+          ("[%d, %d]" % (min(wl), max(wl)) if wl else "none", max(sw) if sw else "none", sorted(set(dist))))
 
     G, groups = (W + 3) // 4, (H + 3) // 4
     pooled = any(b["padd"] for b in bl)
