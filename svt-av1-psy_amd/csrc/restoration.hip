@@ -25,6 +25,12 @@ constexpr size_t lr_frame_mid(const int ur) { return (size_t)(ur + 6) * 64 * 2; 
 constexpr size_t lr_frame_ab(const int ur) { return lr_frame_a(ur) + (size_t)(ur + 2) * 66 * 4; }
 constexpr size_t lr_frame_union(const int ur) { return lr_frame_ab(ur) > lr_frame_mid(ur) ? lr_frame_ab(ur) : lr_frame_mid(ur); }
 constexpr size_t lr_frame_smem(const int ur) { return (size_t)(ur + 6) * TW * 2 + lr_frame_union(ur) + 512; }
+// Columns of a workgroup: the processing unit's 64 >> ss_x, or the restoration unit's width where that is smaller -- the reference walks its processing units inside
+// each restoration unit (restoration.c:1076-1125), so a workgroup must never span two of them: it takes ONE unit's filter.  (Rows: unit_size >= 64 >> ss_y is required.)
+__host__ __device__ __forceinline__ int lr_unit_cols(const SvtHipLrParams& P) {
+    const int cw = 64 >> P.ss_x, us = (int)P.unit_size;
+    return us > 0 && us < cw ? us : cw;
+}
 // grid (unit columns, halves of a stripe, stripes); nhu x nvu restoration units, ushift = log2(unit_size) or -1 (the host does the divisions once)
 template <int LR_UR> // rows of a stripe per workgroup: 32 (two workgroups per 64-row luma stripe) or 64
 __global__ __launch_bounds__(256) void lr_frame_kernel(const SvtHipLrParams P, const int nhu, const int nvu, const int ushift, const int stripe0 /* first stripe of the launch */) {
@@ -35,7 +41,7 @@ __global__ __launch_bounds__(256) void lr_frame_kernel(const SvtHipLrParams P, c
     int32_t*  B32  = (int32_t*)((uint8_t*)mid + lr_frame_a(LR_UR));
     uint16_t* xlut = (uint16_t*)((uint8_t*)mid + lr_frame_union(LR_UR));
     const int tid = threadIdx.x;
-    const int pw = (int)P.width, ph = (int)P.height, off = 8 >> P.ss_y, sh = 64 >> P.ss_y, cw = 64 >> P.ss_x;
+    const int pw = (int)P.width, ph = (int)P.height, off = 8 >> P.ss_y, sh = 64 >> P.ss_y, cw = lr_unit_cols(P);
     TileSrc s;
     s.data = P.data; s.above = P.boundary_above; s.below = P.boundary_below;
     s.stride = (int)P.stride; s.bstride = (int)P.boundary_stride; s.w = pw; s.h = ph; s.highbd = P.highbd;
@@ -181,7 +187,7 @@ void svt_hip_lr_filter_frame(const SvtHipLrParams* params, void* stream) { svt_h
 void svt_hip_lr_filter_frame_stripes(const SvtHipLrParams* params, int stripe_begin, int stripe_end, void* stream) {
     svthip::ensure_device();
     const SvtHipLrParams& P = *params;
-    const int sh = 64 >> P.ss_y, off = 8 >> P.ss_y, cw = 64 >> P.ss_x;
+    const int sh = 64 >> P.ss_y, off = 8 >> P.ss_y, cw = lr_unit_cols(P);
     const int all_stripes = ((int)P.height + off + sh - 1) / sh;
     if (stripe_end < 0 || stripe_end > all_stripes) stripe_end = all_stripes;
     if (stripe_begin < 0) stripe_begin = 0;
