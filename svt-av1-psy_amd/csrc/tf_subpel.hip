@@ -224,7 +224,7 @@ extern "C" int svt_hip_tf_subpel_search_host(const SvtHipTfSubpelParams* params,
     svthip::HostCallLease lease; // (a pooled arena: see svt_hip_common.h)
     svthip::HostCall& c = *lease;
     c.begin();
-    c.reserve((src_samples + ref_samples) * px + db + rb + 8192, (src_samples + ref_samples) * px + db + rb + 8192);
+    c.reserve((src_samples + ref_samples) * px + db + rb + 8192, (src_samples + ref_samples) * px + db + 2 * rb + 8192);
     void* d_src = c.dalloc(src_samples * px);
     void* d_ref = c.dalloc(ref_samples * px);
     SvtHipTfSubpelDesc*   d_d = (SvtHipTfSubpelDesc*)c.dalloc(db);
@@ -232,6 +232,10 @@ extern "C" int svt_hip_tf_subpel_search_host(const SvtHipTfSubpelParams* params,
     c.up(d_src, src_buf, src_samples * px);
     c.up(d_ref, ref_buf, ref_samples * px);
     c.up(d_d, descs, db);
+    // the kernel writes no result for an unused descriptor (bsize 0): its slot must come back as the caller left it, not as the arena held it
+    bool unused = false;
+    for (uint32_t i = 0; i < n && !unused; i++) unused = descs[i].bsize == 0;
+    if (unused) c.up(d_r, results, rb);
     svt_hip_tf_subpel_search_batch(params, d_src, d_ref, d_d, n, d_r, c.stream);
     c.down(results, d_r, rb);
     return 0;
