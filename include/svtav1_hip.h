@@ -1149,6 +1149,87 @@ int8_t   svt_av1_wedge_sign_from_residuals_hip(const int16_t *ds, const uint8_t 
 void     svt_av1_wedge_compute_delta_squares_hip(int16_t *d, const int16_t *a, const int16_t *b, int N);
 uint64_t svt_aom_sum_squares_i16_hip(const int16_t *src, uint32_t N);
 
+/* ------------------------------------------- AV1 warped motion: block warp filter, local model fit, warp error (csrc/warp.hip) ------------- */
+/* One launch, n blocks of mixed sizes: what svt_av1_warp_affine_c (bit_depth 8, uint8_t samples) / svt_av1_highbd_warp_affine_c (10 / 12, uint16_t samples)
+ * (warped_motion.c:569, :714) leave in dst, bit for bit, with the ConvolveParams plane_warped_motion_prediction builds (enc_inter_prediction.c:2040):
+ * get_conv_params_no_round(0, 0, 0, tmp, 128, is_compound, bd), i.e. round_0 3 (5 at 12 bit), round_1 7 when compound.  Descriptors sit at the level of the dispatch
+ * pointer: the ROTZOOM fix-up of svt_warp_plane, svt_get_shear_params (or svt_hip_warp_model_batch below) and the block geometry are the caller's.
+ *   compound 0 one call, not compound;
+ *   compound 1 what two calls leave in dst: reference 0 with do_average = 0 into a ConvBufType buffer, reference 1 with do_average = 1;
+ *   compound 2 the same with use_jnt_comp_avg = 1 and the two offsets.  The ConvBufType values never reach memory; the two references have independent models,
+ *              planes and bounds.
+ * The reference's arithmetic is reproduced as written: dst_x / dst_y in int32_t, x4 = dst_x >> subsampling_x, the WARP_PARAM_REDUCE_BITS masking of sx4 / sy4, the
+ * high-bit-depth reduce_bits_horiz = round_0 + max(bd + FILTER_BITS - round_0 - 14, 0), the 16-bit unsigned ConvBufType, the cropping of the last 8x8 tile.
+ * READABLE EXTENT: exactly width x height samples at ref_off, rows `stride` apart.  Every coordinate is clamped to [0, width) x [0, height) before the address is
+ * formed, however far outside the model projects: nothing is read at a negative offset or beyond row height - 1 / column width - 1.
+ * planes.base[] are device pointers (uint8_t samples at bit_depth 8, uint16_t at 10 and 12; the reference's split 8-bit + 2-bit planes are handled by the single-call
+ * form only), passed by value; dst_base and descs are device pointers.
+ * INVALID DESCRIPTORS never fault; status == NULL / != NULL and the return value exactly as svt_hip_inter_pred_batch.  A descriptor is invalid when p_width or
+ * p_height is outside 1 .. 128, a sub-sampling is above 1, compound is above 2; width, height or stride of a used reference is below 1; its plane index is >= 32 or
+ * the plane has no base; 4 |alpha| + 7 |beta| >= 65536 or 4 |gamma| + 4 |delta| >= 65536 (is_affine_shear_allowed: what keeps the filter index inside 0 .. 192);
+ * src_x, src_y, dst_x or dst_y of any of its tiles does not fit int32_t when computed in 64 bits (the C computes them in int32_t). */
+typedef struct SvtHipWarpRef {
+    uint64_t ref_off;        /* samples from planes.base[plane]: where the C's `ref` points, i.e. sample (0, 0) of the picture proper */
+    int32_t  mat[6];         /* as svt_av1_warp_affine receives them */
+    int16_t  alpha, beta, gamma, delta;
+    int32_t  width, height, stride; /* the clamp bounds and the row pitch, samples */
+    uint8_t  plane;
+    uint8_t  pad[3];
+} SvtHipWarpRef;
+typedef struct SvtHipWarpDesc {
+    SvtHipWarpRef ref[2];    /* [1] is read only when compound != 0 */
+    uint64_t dst_off;        /* samples from dst_base: the block's first sample */
+    uint32_t dst_stride;
+    int32_t  p_col, p_row;
+    uint8_t  p_width, p_height; /* 1 .. 128, any value */
+    uint8_t  subsampling_x, subsampling_y;
+    uint8_t  compound;       /* 0 / 1 / 2 as SvtHipInterPredDesc.compound */
+    uint8_t  fwd_offset, bck_offset; /* compound == 2 */
+    uint8_t  pad[5];
+} SvtHipWarpDesc;
+int svt_hip_warp_pred_batch(SvtHipInterPredPlanes planes, void *dst_base, const SvtHipWarpDesc *descs, uint32_t n, int bit_depth, uint8_t *status, void *stream);
+/* The local-warp model of n blocks: out[i] is what svt_find_projection(np, pts, pts_inref, bsize, mv_row, mv_col, &wm, mi_row, mi_col) (warped_motion.c:472) leaves
+ * in wm.wmmat[0 .. 5], wm.alpha .. wm.delta, and its return value in `invalid` -- find_affine_int followed by svt_get_shear_params, in plain integer arithmetic: the
+ * LS_* sums in int32_t, the 64-bit determinant, resolve_divisor_64 / _32 with the generated table (entry n = round(2^22 / (256 + n))), the 64-bit get_mult_shift_*
+ * pair (USE_LIMITED_PREC_MULT 0), the clamps, the int16_t narrowing of i_det and of its left shift, the WARP_PARAM_REDUCE_BITS rounding.  When the C returns 1,
+ * invalid = 1 and every other field is 0.  svt_aom_select_samples and the neighbour scan are the caller's.  descs, out, status are device pointers; out[i] feeds a
+ * SvtHipWarpRef without a host round trip.  INVALID DESCRIPTORS (np outside 1 .. 8, bsize >= 22): status / return value as svt_hip_inter_pred_batch; the result of
+ * an invalid descriptor is not written. */
+typedef struct SvtHipWarpModelDesc {
+    int32_t pts[16], pts_inref[16]; /* x, y pairs, 1/8 sample, relative to the block's origin as svt_find_projection takes them */
+    int32_t np;              /* 1 .. 8 */
+    int32_t mi_row, mi_col;
+    int16_t mv_row, mv_col;  /* the C's mvy, mvx */
+    uint8_t bsize;           /* BlockSize */
+    uint8_t pad[3];
+} SvtHipWarpModelDesc;
+typedef struct SvtHipWarpModel {
+    int32_t wmmat[6];
+    int16_t alpha, beta, gamma, delta;
+    uint8_t invalid;         /* svt_find_projection's return value */
+    uint8_t pad[3];
+} SvtHipWarpModel;
+int svt_hip_warp_model_batch(const SvtHipWarpModelDesc *descs, uint32_t n, SvtHipWarpModel *out, uint8_t *status, void *stream);
+/* The warp error of n candidate models over a picture, 8 bit (as global motion runs): out[i] is what warp_error (enc_warped_motion.c:22) returns with
+ * best_error = INT64_MAX -- the SAD between the source and the warp (get_conv_params(0, 0, 0, 8), not compound) over the 32 x 32 error blocks: all of them for
+ * chess_refn == 0, the checkerboard half (jstart alternating by block row as written there), times two, for chess_refn == 1.  The warped samples never reach memory.
+ * The C's EARLY EXIT returns a partial sum and is not reproduced: partial sums are monotone, so the C leaves early iff the full, undoubled sum exceeds best_error --
+ * comparing out[i] (halved when chess_refn == 1) against best_error gives the same decision.  svt_av1_warp_error's own call of svt_get_shear_params is the caller's:
+ * `ref` carries alpha .. delta.  src_off points at sample (0, 0) of the source picture: sample (x, y) of the block is read at src_off + y * src_stride + x with
+ * x from p_col, y from p_row.  The sums are exact integers added with 64-bit atomics into out, which the entry zeroes first: the result does not depend on the order.
+ * INVALID DESCRIPTORS (those of the reference in svt_hip_warp_pred_batch; p_width or p_height outside 1 .. 65536; a sub-sampling or chess_refn above 1; src_stride
+ * below 1; src_plane >= 32 or without a base): status / return value as svt_hip_inter_pred_batch, out[i] of an invalid descriptor is 0.  n <= 65535. */
+typedef struct SvtHipWarpErrorDesc {
+    SvtHipWarpRef ref;
+    uint64_t src_off;        /* samples from planes.base[src_plane] */
+    uint32_t src_stride;
+    int32_t  p_col, p_row, p_width, p_height;
+    uint8_t  src_plane;
+    uint8_t  subsampling_x, subsampling_y, chess_refn;
+} SvtHipWarpErrorDesc;
+int svt_hip_warp_error_batch(SvtHipInterPredPlanes planes, const SvtHipWarpErrorDesc *descs, uint32_t n, uint64_t *out, uint8_t *status, void *stream);
+/* (the two single-call forms are declared next to SvtHipConvolveParams, further down) */
+
 /* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
 #define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
 #define SVT_HIP_BLOCK_MEAN_PREC_SUB  1
@@ -1409,6 +1490,18 @@ void svt_aom_highbd_blend_a64_d16_mask_hip(uint8_t *dst, uint32_t dst_stride, co
                                            const int bd);
 void svt_av1_build_compound_diffwtd_mask_d16_hip(uint8_t *mask, uint8_t mask_type, const uint16_t *src0, int src0_stride, const uint16_t *src1, int src1_stride, int h,
                                                  int w, SvtHipConvolveParams *conv_params, int bd);
+/* the two warp forms (csrc/warp.hip; common_dsp_rtcd.h:1032, :1035; exported, NOT installed by svt_hip_setup_rtcd: INTEGRATION.md).  Host pointers.  The forms honour
+ * conv_params->round_0 / round_1 / is_compound / do_average / use_jnt_comp_avg / fwd_offset / bck_offset / dst / dst_stride as the C does: is_compound with
+ * do_average == 0 writes the ConvBufType buffer and leaves pred untouched.  The high-bit-depth form packs (ref8b << 2) | ((ref2b >> 6) & 3).  Only the sample
+ * rectangle the call can read after clamping is copied to the device, never a sample outside width x height.  ACCEPTED RANGE, outside of which nothing is written:
+ * the roundings as for the jnt_ forms (0 <= round_0 <= 7, round_1 >= 0, round_0 + round_1 <= 14, round_1 <= 7 when is_compound); p_width, p_height 1 .. 128; the
+ * conditions of svt_hip_warp_pred_batch on sub-sampling, bounds, shear and the int32_t range; bd 10 or 12 in the highbd form. */
+void svt_av1_warp_affine_hip(const int32_t *mat, const uint8_t *ref, int width, int height, int stride, uint8_t *pred, int p_col, int p_row, int p_width,
+                             int p_height, int p_stride, int subsampling_x, int subsampling_y, SvtHipConvolveParams *conv_params, int16_t alpha, int16_t beta,
+                             int16_t gamma, int16_t delta);
+void svt_av1_highbd_warp_affine_hip(const int32_t *mat, const uint8_t *ref8b, const uint8_t *ref2b, int width, int height, int stride8b, int stride2b,
+                                    uint16_t *pred, int p_col, int p_row, int p_width, int p_height, int p_stride, int subsampling_x, int subsampling_y, int bd,
+                                    SvtHipConvolveParams *conv_params, int16_t alpha, int16_t beta, int16_t gamma, int16_t delta);
 /* the sixteen inter-prediction forms (csrc/interpred.hip; described with svt_hip_inter_pred_batch above) */
 #define SVT_HIP_DECLARE_CONVOLVE(name)                                                                                                                               \
     void svt_av1_##name##_hip(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w, int32_t h,                                        \

@@ -362,6 +362,26 @@ PROTOTYPES["svt_av1_wedge_compute_delta_squares_hip"] = (None, [vp, vp, vp, C.c_
 PROTOTYPES["svt_aom_sum_squares_i16_hip"] = (C.c_uint64, [vp, C.c_uint32])
 
 
+# AV1 warped motion (csrc/warp.hip): SvtHipWarpRef, SvtHipWarpDesc, SvtHipWarpModelDesc, SvtHipWarpModel, SvtHipWarpErrorDesc
+WARP_DESCS_PER_WORKGROUP = 16  # descriptors one workgroup of svt_hip_warp_pred_batch flattens into its tile list
+WarpRef = np.dtype([("ref_off", "<u8"), ("mat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("width", "<i4"), ("height", "<i4"),
+                    ("stride", "<i4"), ("plane", "u1"), ("pad", "u1", (3,))])
+WarpDesc = np.dtype([("ref", WarpRef, (2,)), ("dst_off", "<u8"), ("dst_stride", "<u4"), ("p_col", "<i4"), ("p_row", "<i4"), ("p_width", "u1"), ("p_height", "u1"),
+                     ("subsampling_x", "u1"), ("subsampling_y", "u1"), ("compound", "u1"), ("fwd_offset", "u1"), ("bck_offset", "u1"), ("pad", "u1", (5,))])
+WarpModelDesc = np.dtype([("pts", "<i4", (16,)), ("pts_inref", "<i4", (16,)), ("np", "<i4"), ("mi_row", "<i4"), ("mi_col", "<i4"), ("mv_row", "<i2"), ("mv_col", "<i2"),
+                          ("bsize", "u1"), ("pad", "u1", (3,))])
+WarpModel = np.dtype([("wmmat", "<i4", (6,)), ("alpha", "<i2"), ("beta", "<i2"), ("gamma", "<i2"), ("delta", "<i2"), ("invalid", "u1"), ("pad", "u1", (3,))])
+WarpErrorDesc = np.dtype([("ref", WarpRef), ("src_off", "<u8"), ("src_stride", "<u4"), ("p_col", "<i4"), ("p_row", "<i4"), ("p_width", "<i4"), ("p_height", "<i4"),
+                          ("src_plane", "u1"), ("subsampling_x", "u1"), ("subsampling_y", "u1"), ("chess_refn", "u1")])
+assert WarpRef.itemsize == 56 and WarpDesc.itemsize == 144 and WarpModelDesc.itemsize == 148 and WarpModel.itemsize == 36 and WarpErrorDesc.itemsize == 88
+PROTOTYPES["svt_hip_warp_pred_batch"] = (C.c_int, [InterPredPlanes, vp, vp, C.c_uint32, C.c_int, vp, vp])
+PROTOTYPES["svt_hip_warp_model_batch"] = (C.c_int, [vp, C.c_uint32, vp, vp, vp])
+PROTOTYPES["svt_hip_warp_error_batch"] = (C.c_int, [InterPredPlanes, vp, C.c_uint32, vp, vp, vp])
+_WA = [C.c_int] * 7 + [vp] + [C.c_int16] * 4  # p_col .. subsampling_y, conv_params, alpha .. delta
+PROTOTYPES["svt_av1_warp_affine_hip"] = (None, [vp, vp, C.c_int, C.c_int, C.c_int, vp] + _WA)
+PROTOTYPES["svt_av1_highbd_warp_affine_hip"] = (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 8 + [vp] + [C.c_int16] * 4)
+
+
 # picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
 BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
 VarBoostFrame = np.dtype([("normalized_base_q_idx", "<i4"), ("min_qindex", "<i4"), ("max_qindex", "<i4"), ("reserved", "<i4")])
