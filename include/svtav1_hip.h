@@ -1230,6 +1230,146 @@ typedef struct SvtHipWarpErrorDesc {
 int svt_hip_warp_error_batch(SvtHipInterPredPlanes planes, const SvtHipWarpErrorDesc *descs, uint32_t n, uint64_t *out, uint8_t *status, void *stream);
 /* (the two single-call forms are declared next to SvtHipConvolveParams, further down) */
 
+/* ------------------------------------------- block variance family and the MD sub-pel motion search (csrc/mdsubpel.hip) -------------------- */
+/* The AomVarianceFnPtr primitives of svt_aom_mefn_ptr (av1me.c:29-197) for n blocks of mixed sizes in one launch, 8-bit luma.  bsize is a BlockSize 0 .. 21 (the 22
+ * sizes of VARIANCES(W, H), variance.c:324-345).  Per block, by kind:
+ *   VAR          svt_aom_variance{W}x{H}_c(pre, pre_stride, src, src_stride, &sse): var, sse, sum (sum of pre - src);
+ *   SUBPIX       svt_aom_sub_pixel_variance{W}x{H}_c(pre, pre_stride, xoffset, yoffset, src, src_stride, &sse): bilinear_filters_2t, two roundings (+64 >> 7 each,
+ *                horizontal to uint16_t, vertical to uint8_t), offsets 0 .. 7;
+ *   UPSAMPLED    svt_aom_upsampled_pred_c(.., W, H, xoffset, yoffset, pre, pre_stride, taps) followed by vf against src -- what svt_upsampled_pref_error computes.
+ *                taps 1 / 2 / 3 = USE_2_TAPS / USE_4_TAPS / USE_8_TAPS.  svt_aom_convolve8_horiz_c then _vert_c: always 8 taps wide, each stage rounds by 7 and clips
+ *                to 8 bits, phase q3 << 1 of av1_interp_4tap[BILINEAR], av1_sub_pel_filters_4, av1_sub_pel_filters_8;
+ *   MSE          svt_aom_mse16x16_c: sse (var repeats it, sum is 0); bsize must be BLOCK_16X16;
+ *   OBMC_SAD     svt_aom_obmc_sad{W}x{H}_c(pre, pre_stride, wsrc, mask): sad (the other fields 0);
+ *   OBMC_VAR     svt_aom_obmc_variance{W}x{H}_c: var, sse, sum of ROUND_POWER_OF_TWO_SIGNED(wsrc - pre * mask, 12);
+ *   OBMC_SUBPIX  svt_aom_obmc_sub_pixel_variance{W}x{H}_c: the same on the bilinear prediction.
+ * var = sse - (uint32_t)(((int64_t)sum * sum) / (W * H)); sse is the C's wrapping uint32_t sum.  Fields a kind does not produce are written as 0.
+ * READABLE EXTENT, never more than the C reads: W x H of pre for VAR, MSE, OBMC_SAD, OBMC_VAR; (W + 1) x (H + 1) for SUBPIX, OBMC_SUBPIX (column W only with
+ * xoffset != 0, row H only with yoffset != 0); UPSAMPLED: the block itself when both offsets are 0, columns -3 .. W + 3 of the block's rows when only x is
+ * fractional, rows -3 .. H + 3 of the block's columns when only y is, columns -3 .. W + 3 of rows -3 .. H + 3 when both are.  W x H of src; W * H contiguous int32_t
+ * of wsrc and of mask.  No vector is clamped to a picture: padding is the caller's.
+ * planes.base[] (passed by value), src_base, wsrc_base, mask_base, descs, out, status are device pointers.
+ * INVALID DESCRIPTORS (bsize >= 22; kind > 6; an offset above 7 where the kind reads it; UPSAMPLED with taps outside 1 .. 3; MSE at another size; a plane index
+ * >= 32 or without a base; a kind whose src_base / wsrc_base / mask_base is NULL) never fault: status == NULL / != NULL and the return value exactly as
+ * svt_hip_inter_pred_batch; the result of an invalid descriptor is not written. */
+#define SVT_HIP_VAR_VAR         0
+#define SVT_HIP_VAR_SUBPIX      1
+#define SVT_HIP_VAR_UPSAMPLED   2
+#define SVT_HIP_VAR_MSE         3
+#define SVT_HIP_VAR_OBMC_SAD    4
+#define SVT_HIP_VAR_OBMC_VAR    5
+#define SVT_HIP_VAR_OBMC_SUBPIX 6
+typedef struct SvtHipBlockVarDesc {
+    uint64_t pre_off;        /* samples from planes.base[pre_plane]: the C's first argument */
+    uint64_t src_off;        /* bytes from src_base */
+    uint64_t wsrc_off;       /* OBMC kinds: int32_t elements from wsrc_base */
+    uint64_t mask_off;       /* OBMC kinds: int32_t elements from mask_base */
+    uint32_t pre_stride, src_stride;
+    uint8_t  pre_plane;
+    uint8_t  bsize;          /* BlockSize 0 .. 21 */
+    uint8_t  kind;           /* SVT_HIP_VAR_* */
+    uint8_t  xoffset, yoffset; /* 0 .. 7 */
+    uint8_t  taps;           /* UPSAMPLED: 1 .. 3 */
+    uint8_t  pad[2];
+} SvtHipBlockVarDesc;
+typedef struct SvtHipBlockVarResult {
+    uint32_t var, sse;
+    int32_t  sum;
+    uint32_t sad;
+} SvtHipBlockVarResult;
+int svt_hip_block_var_batch(SvtHipInterPredPlanes planes, const uint8_t *src_base, const int32_t *wsrc_base, const int32_t *mask_base, const SvtHipBlockVarDesc *descs,
+                            uint32_t n, SvtHipBlockVarResult *out, uint8_t *status, void *stream);
+/* n (block, reference) sub-pel searches in one launch: one item is one call of md_subpel_search (product_coding_loop.c:2631), i.e. of
+ * svt_av1_find_best_sub_pixel_tree (method 0) or svt_av1_find_best_sub_pixel_tree_pruned (method 1) (mcomp.c:688, :606) with is_scaled == 0, 8-bit luma, complete:
+ *   tree    centre error (svt_upsampled_setup_center_error); the PD_PASS_1 round reduction from mvp_th / hp_mv_th (mvp_th == 0 switches it off: what ictx == NULL or
+ *           another pass gives); early returns in the order early_exit, pred_variance_th (variance against the constant 128 of svt_aom_eb_av1_var_offs,
+ *           ROUND_POWER_OF_TWO by num_pels_log2), abs_th_mult with (w * h) >> 2, round == 0; svt_first_level_check, svt_second_level_check_v2 when
+ *           iters_per_step > 1; candidates by svt_upsampled_pref_error (UPSAMPLED above with subpel_search_type as taps);
+ *   pruned  early returns in the order early_exit, abs_th_mult with (w * h) >> 3, round == 0, pred_variance_th; org_error from skip_diag_refinement 0 / 1 / 2,3 / >= 4
+ *           with the w >= 64 || h >= 64 divisor; two_level_checks_fast; the round_dev_th deviation exit; candidates by svf (SUBPIX above); the MV_COST_OPT
+ *           pre-evaluation exit of svt_check_better_fast.
+ * Common: svt_mv_err_cost for the six MV_COST_TYPE values (ENTROPY reads tables[cost_table]: joint[4] and comp[2][MV_VALS] centred at MV_MAX, the difference
+ * clipped at MV_LOW .. MV_UPP as svt_mv_cost does -- the one index that clip leaves outside either end of a table reads the end entry; cost_table < 0 or
+ * tables == NULL is the C's mvcost == NULL: cost 0); bias_fp while the running best is full-pel; the (uint64_t)cost * weight / 100 < besterr comparison; INT_MAX for
+ * candidates outside the limits; vectors narrowed to int16_t as MV does.
+ * The reference position: ref_off is where the block sits in the reference picture (vector 0, 0); a candidate reads planes.base[ref_plane] + ref_off +
+ * (row >> 3) * ref_stride + (col >> 3) with the extent of its kind above -- no vector is clamped, the limits and the picture's padding are the caller's.
+ * Inside the encoder an item's ref_mv and early_exit come from neighbours that are already decided, so a batch spans the (list, reference, block size) candidates a
+ * caller has in hand, not a frame.
+ * INVALID DESCRIPTORS (bsize >= 22; method > 1; forced_stop > 3; subpel_search_type outside 1 .. 3; mv_cost_type > 5; cost_table >= n_tables; a plane index >= 32
+ * or without a base) never fault: status / return value exactly as svt_hip_inter_pred_batch; the result of an invalid descriptor is not written. */
+#define SVT_HIP_MV_VALS 32767 /* MV_VALS (cabac_context_model.h:521) */
+typedef struct SvtHipMvCostTable {
+    int32_t joint[4];                  /* mvjcost, by MvJointType */
+    int32_t comp[2][SVT_HIP_MV_VALS];  /* mvcost[0] (row), mvcost[1] (col): entry [MV_MAX + v] is the C's mvcost[k][v] */
+} SvtHipMvCostTable;
+typedef struct SvtHipMdSubpelDesc {
+    uint64_t src_off;        /* bytes from src_base: the block's first source sample */
+    uint64_t ref_off;        /* samples from planes.base[ref_plane]: the block's position in the reference */
+    uint32_t src_stride, ref_stride;
+    int32_t  lim_col_min, lim_col_max, lim_row_min, lim_row_max; /* SubpelMvLimits (svt_hip_md_subpel_mv_limits) */
+    int32_t  pred_variance_th, round_dev_th, bias_fp;
+    int32_t  error_per_bit, early_exit_th; /* MV_COST_PARAMS */
+    int32_t  cost_table;     /* MV_COST_ENTROPY: index into tables, < 0: none */
+    int32_t  qp;
+    int32_t  hp_mv_th;       /* md_subpel_me_ctrls.hp_mv_th */
+    uint32_t best_mvp_err;   /* ctx->best_fp_mvp_dist[list][ref] */
+    int16_t  best_mvp_row, best_mvp_col; /* ctx->mvp_array[list][ref][best_fp_mvp_idx] */
+    int16_t  start_mv_row, start_mv_col; /* 1/8 sample: subpel_start_mv */
+    int16_t  ref_mv_row, ref_mv_col;
+    uint8_t  ref_plane;
+    uint8_t  bsize;
+    uint8_t  method;         /* 0 SUBPEL_TREE, 1 SUBPEL_TREE_PRUNED */
+    uint8_t  allow_hp;
+    uint8_t  forced_stop;    /* SUBPEL_FORCE_STOP: 0 EIGHTH_PEL .. 3 FULL_PEL */
+    uint8_t  iters_per_step;
+    uint8_t  abs_th_mult;
+    uint8_t  skip_diag_refinement;
+    uint8_t  subpel_search_type; /* 1 .. 3: USE_2_TAPS, USE_4_TAPS, USE_8_TAPS (tree) */
+    uint8_t  mv_cost_type;   /* MV_COST_TYPE 0 .. 5 */
+    uint8_t  early_exit;     /* early_neigh_check_exit */
+    uint8_t  mvp_th;         /* md_subpel_me_ctrls.mvp_th; 0: the rule is off */
+    uint8_t  pad[4];
+} SvtHipMdSubpelDesc; /* 104 bytes */
+typedef struct SvtHipMdSubpelResult {
+    int16_t  mv_row, mv_col; /* *bestmv */
+    uint32_t besterr;        /* the return value */
+    int32_t  distortion;     /* *distortion */
+    uint32_t sse1;           /* *sse1 of a caller that set it to 0 before the call */
+    uint32_t fp_me_dist;     /* the centre error, what goes to ctx->fp_me_dist */
+    uint32_t evals;          /* predictions compared with the source, the centre included (a measurement aid) */
+} SvtHipMdSubpelResult;
+int svt_hip_md_subpel_search_batch(SvtHipInterPredPlanes planes, const uint8_t *src_base, const SvtHipMvCostTable *tables, uint32_t n_tables,
+                                   const SvtHipMdSubpelDesc *descs, uint32_t n, SvtHipMdSubpelResult *out, uint8_t *status, void *stream);
+/* Host helper: the four SubpelMvLimits as md_subpel_search derives them (:2656-2666) -- the UMV window of the block, svt_av1_set_mv_search_range and
+ * svt_av1_set_subpel_mv_search_range restated.  limits = col_min, col_max, row_min, row_max.  Returns 0, or -1 (nothing written) for bsize >= 22 or a NULL limits. */
+int svt_hip_md_subpel_mv_limits(int mi_row, int mi_col, int bsize, int mi_rows, int mi_cols, int16_t ref_mv_row, int16_t ref_mv_col, int32_t *limits);
+/* single-call forms with the reference's prototypes (aom_dsp_rtcd.h; exported, NOT installed by svt_hip_setup_rtcd: INTEGRATION.md).  Host pointers, the readable
+ * extents above.  On a device error, a NULL pointer or an offset above 7 nothing is written and the value forms return 0. */
+#define SVT_HIP_VARIANCE_DECL(W, H)                                                                                                                                      \
+    unsigned int svt_aom_variance##W##x##H##_hip(const uint8_t *src_ptr, int source_stride, const uint8_t *ref_ptr, int ref_stride, unsigned int *sse);                  \
+    uint32_t     svt_aom_sub_pixel_variance##W##x##H##_hip(const uint8_t *src_ptr, int source_stride, int xoffset, int yoffset, const uint8_t *ref_ptr, int ref_stride,   \
+                                                       uint32_t *sse);                                                                                                  \
+    unsigned int svt_aom_obmc_sad##W##x##H##_hip(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask);                                          \
+    unsigned int svt_aom_obmc_variance##W##x##H##_hip(const uint8_t *pre, int pre_stride, const int32_t *wsrc, const int32_t *mask, unsigned int *sse);                  \
+    unsigned int svt_aom_obmc_sub_pixel_variance##W##x##H##_hip(const uint8_t *pre, int pre_stride, int xoffset, int yoffset, const int32_t *wsrc, const int32_t *mask,  \
+                                                            unsigned int *sse);
+#define SVT_HIP_FOR_ALL_VARIANCE_SIZES(X)                                                                                                             \
+    X(128, 128) X(128, 64) X(64, 128) X(64, 64) X(64, 32) X(32, 64) X(32, 32) X(32, 16) X(16, 32) X(16, 16) X(16, 8) X(8, 16) X(8, 8) X(8, 4) X(4, 8) \
+    X(4, 4) X(4, 16) X(16, 4) X(8, 32) X(32, 8) X(16, 64) X(64, 16)
+SVT_HIP_FOR_ALL_VARIANCE_SIZES(SVT_HIP_VARIANCE_DECL)
+#undef SVT_HIP_VARIANCE_DECL
+uint32_t svt_aom_mse16x16_hip(const uint8_t *src_ptr, int32_t source_stride, const uint8_t *ref_ptr, int32_t recon_stride, uint32_t *sse);
+/* svt_aom_upsampled_pred: writes the width x height prediction (packed, row pitch `width`) to comp_pred; xd, cm, mi_row, mi_col, mv are not read, as in the C.
+ * width, height powers of two 4 .. 128, subpel_search 1 .. 3, otherwise nothing is written. */
+#ifdef SVT_HIP_REFERENCE_TYPES
+void svt_aom_upsampled_pred_hip(MacroBlockD *xd, const struct AV1Common *const cm, int mi_row, int mi_col, const MV *const mv, uint8_t *comp_pred, int width, int height,
+                                int subpel_x_q3, int subpel_y_q3, const uint8_t *ref, int ref_stride, int subpel_search);
+#else
+void svt_aom_upsampled_pred_hip(void *xd, const void *cm, int mi_row, int mi_col, const SvtHipMv *mv, uint8_t *comp_pred, int width, int height, int subpel_x_q3,
+                                int subpel_y_q3, const uint8_t *ref, int ref_stride, int subpel_search);
+#endif
+
 /* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
 #define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
 #define SVT_HIP_BLOCK_MEAN_PREC_SUB  1

@@ -382,6 +382,38 @@ PROTOTYPES["svt_av1_warp_affine_hip"] = (None, [vp, vp, C.c_int, C.c_int, C.c_in
 PROTOTYPES["svt_av1_highbd_warp_affine_hip"] = (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 8 + [vp] + [C.c_int16] * 4)
 
 
+# block variance family and the MD sub-pel search (csrc/mdsubpel.hip): SvtHipBlockVarDesc, SvtHipBlockVarResult, SvtHipMvCostTable, SvtHipMdSubpelDesc, SvtHipMdSubpelResult
+VAR_VAR, VAR_SUBPIX, VAR_UPSAMPLED, VAR_MSE, VAR_OBMC_SAD, VAR_OBMC_VAR, VAR_OBMC_SUBPIX = range(7)
+MV_VALS = 32767
+MDSUBPEL_SMALL_PIXELS = 4096  # blocks above this many pixels run in the one-wave-per-workgroup launch class
+MDSUBPEL_WAVES_PER_WORKGROUP = 4  # items (one wave each) of one workgroup of the other class
+VARIANCE_SIZES = [(128, 128), (128, 64), (64, 128), (64, 64), (64, 32), (32, 64), (32, 32), (32, 16), (16, 32), (16, 16), (16, 8), (8, 16), (8, 8), (8, 4), (4, 8),
+                  (4, 4), (4, 16), (16, 4), (8, 32), (32, 8), (16, 64), (64, 16)]  # VARIANCES(W, H), variance.c:324-345
+BlockVarDesc = np.dtype([("pre_off", "<u8"), ("src_off", "<u8"), ("wsrc_off", "<u8"), ("mask_off", "<u8"), ("pre_stride", "<u4"), ("src_stride", "<u4"),
+                         ("pre_plane", "u1"), ("bsize", "u1"), ("kind", "u1"), ("xoffset", "u1"), ("yoffset", "u1"), ("taps", "u1"), ("pad", "u1", (2,))])
+BlockVarResult = np.dtype([("var", "<u4"), ("sse", "<u4"), ("sum", "<i4"), ("sad", "<u4")])
+MvCostTable = np.dtype([("joint", "<i4", (4,)), ("comp", "<i4", (2, MV_VALS))])
+MdSubpelDesc = np.dtype([("src_off", "<u8"), ("ref_off", "<u8"), ("src_stride", "<u4"), ("ref_stride", "<u4"), ("lim_col_min", "<i4"), ("lim_col_max", "<i4"),
+                         ("lim_row_min", "<i4"), ("lim_row_max", "<i4"), ("pred_variance_th", "<i4"), ("round_dev_th", "<i4"), ("bias_fp", "<i4"),
+                         ("error_per_bit", "<i4"), ("early_exit_th", "<i4"), ("cost_table", "<i4"), ("qp", "<i4"), ("hp_mv_th", "<i4"), ("best_mvp_err", "<u4"),
+                         ("best_mvp_row", "<i2"), ("best_mvp_col", "<i2"), ("start_mv_row", "<i2"), ("start_mv_col", "<i2"), ("ref_mv_row", "<i2"), ("ref_mv_col", "<i2"),
+                         ("ref_plane", "u1"), ("bsize", "u1"), ("method", "u1"), ("allow_hp", "u1"), ("forced_stop", "u1"), ("iters_per_step", "u1"), ("abs_th_mult", "u1"),
+                         ("skip_diag_refinement", "u1"), ("subpel_search_type", "u1"), ("mv_cost_type", "u1"), ("early_exit", "u1"), ("mvp_th", "u1"), ("pad", "u1", (4,))])
+MdSubpelResult = np.dtype([("mv_row", "<i2"), ("mv_col", "<i2"), ("besterr", "<u4"), ("distortion", "<i4"), ("sse1", "<u4"), ("fp_me_dist", "<u4"), ("evals", "<u4")])
+assert BlockVarDesc.itemsize == 48 and BlockVarResult.itemsize == 16 and MvCostTable.itemsize == 262152 and MdSubpelDesc.itemsize == 104 and MdSubpelResult.itemsize == 24
+PROTOTYPES["svt_hip_block_var_batch"] = (C.c_int, [InterPredPlanes, vp, vp, vp, vp, C.c_uint32, vp, vp, vp])
+PROTOTYPES["svt_hip_md_subpel_search_batch"] = (C.c_int, [InterPredPlanes, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp])
+PROTOTYPES["svt_hip_md_subpel_mv_limits"] = (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int16, C.c_int16, vp])
+for _w, _h in VARIANCE_SIZES:
+    PROTOTYPES["svt_aom_variance%dx%d_hip" % (_w, _h)] = (C.c_uint32, [vp, C.c_int, vp, C.c_int, vp])
+    PROTOTYPES["svt_aom_sub_pixel_variance%dx%d_hip" % (_w, _h)] = (C.c_uint32, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp])
+    PROTOTYPES["svt_aom_obmc_sad%dx%d_hip" % (_w, _h)] = (C.c_uint32, [vp, C.c_int, vp, vp])
+    PROTOTYPES["svt_aom_obmc_variance%dx%d_hip" % (_w, _h)] = (C.c_uint32, [vp, C.c_int, vp, vp, vp])
+    PROTOTYPES["svt_aom_obmc_sub_pixel_variance%dx%d_hip" % (_w, _h)] = (C.c_uint32, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp])
+PROTOTYPES["svt_aom_mse16x16_hip"] = (C.c_uint32, [vp, C.c_int32, vp, C.c_int32, vp])
+PROTOTYPES["svt_aom_upsampled_pred_hip"] = (None, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int])
+
+
 # picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
 BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1
 VarBoostFrame = np.dtype([("normalized_base_q_idx", "<i4"), ("min_qindex", "<i4"), ("max_qindex", "<i4"), ("reserved", "<i4")])
