@@ -1230,6 +1230,95 @@ typedef struct SvtHipWarpErrorDesc {
 int svt_hip_warp_error_batch(SvtHipInterPredPlanes planes, const SvtHipWarpErrorDesc *descs, uint32_t n, uint64_t *out, uint8_t *status, void *stream);
 /* (the two single-call forms are declared next to SvtHipConvolveParams, further down) */
 
+/* ------------------------------------------- pictures of another size: scaled prediction, resize, super-res upscale (csrc/scale.hip) ------- */
+/* A. One launch, n blocks of mixed sizes predicted from references of another size: what svt_av1_convolve_2d_scale / svt_av1_highbd_convolve_2d_scale
+ * (common_dsp_rtcd.h: svt_av1_convolve_2d_scale, svt_av1_highbd_convolve_2d_scale -> inter_prediction.c:420, :779) compute, bit for bit.  Descriptors follow
+ * SvtHipInterPredDesc; the position arithmetic (svt_av1_setup_scale_factors_for_frame, scaled_x / scaled_y, the clamp of compute_subpel_params,
+ * enc_inter_prediction.c:3158-3197) is the caller's, as the MV clamp is there.  Per reference k:
+ *   scaled     xs[k] != 1024 || ys[k] != 1024: svt_av1_[highbd_]convolve_2d_scale_c -- both directions are always filtered (a direction whose step is 1024 too),
+ *              round_0 / round_1 of get_conv_params_no_round, the int16_t intermediate, the 16-bit ConvBufType result (compound or not), the filter following w and h
+ *              through av1_get_interp_filter_params_with_block_size.
+ *   unscaled   xs[k] == ys[k] == 1024: the unscaled case of svt_hip_inter_pred_batch with phase subpel >> 6 (the reference calls svt_aom_convolve[..] for it,
+ *              inter_prediction.c:1312-1380); a remainder in the low 6 bits makes the descriptor invalid.  A descriptor whose references are all unscaled is valid
+ *              and equals svt_hip_inter_pred_batch: the caller need not split its list.
+ *   compound   0 / 1 / 2 and the two offsets as in svt_hip_inter_pred_batch; the ConvBufType buffer never reaches memory.
+ * READABLE EXTENT of a scaled reference, around where src_off points: columns -3 .. (((w - 1) * xs + subpel_x) >> 10) + 4, rows -3 .. (((h - 1) * ys + subpel_y)
+ * >> 10) + 4; of an unscaled one: as svt_hip_inter_pred_batch.  The kernel reads nothing outside.
+ * INVALID DESCRIPTORS (w or h not one of 2, 4, .. 128; a phase above 1023; a step outside 64 .. 2048, the range valid_ref_frame_size allows; an unscaled reference
+ * with a low-6-bit remainder; (((h - 1) * ys + subpel_y) >> 10) + 8 > 2 * 128 + 8, the C's im_block bound, or the same in x; a filter above 3; compound above 2; a
+ * plane index >= 32 or without a base) never fault: status == NULL / != NULL and the return value exactly as svt_hip_inter_pred_batch. */
+typedef struct SvtHipScaledPredDesc {
+    uint64_t src_off[2];     /* samples from planes.base[plane[k]]: where the C's `src` argument points, the clamped position >> SCALE_SUBPEL_BITS */
+    uint64_t dst_off;        /* samples from dst_base */
+    uint32_t src_stride[2], dst_stride; /* samples */
+    uint16_t subpel_x[2], subpel_y[2];  /* SubpelParams after & SCALE_SUBPEL_MASK, 0 .. 1023, per reference */
+    uint16_t xs[2], ys[2];   /* x_step_q4 / y_step_q4, 64 .. 2048; 1024 = not scaled in that direction */
+    uint8_t  plane[2];
+    uint8_t  w, h;           /* 2, 4, 8, .. 128, independently */
+    uint8_t  filter_x, filter_y; /* InterpFilter 0 .. 3 */
+    uint8_t  compound;       /* 0 single reference, 1 average, 2 distance-weighted */
+    uint8_t  fwd_offset, bck_offset; /* compound == 2 */
+    uint8_t  pad[3];
+} SvtHipScaledPredDesc; /* 64 bytes */
+int svt_hip_inter_pred_scaled_batch(SvtHipInterPredPlanes planes, void *dst_base, const SvtHipScaledPredDesc *descs, uint32_t n, int bit_depth, uint8_t *status,
+                                    void *stream);
+/* (the two single-call forms are declared next to SvtHipConvolveParams, further down) */
+
+/* B. The non-normative picture resize, n planes per call: what svt_av1_resize_plane / svt_av1_highbd_resize_plane (aom_dsp_rtcd.h:900-903 -> resize.c:400, :680)
+ * leave in dst, bit for bit -- resize_multistep whole (get_down2_steps, the even and odd half-band filters, the final interpolate with choose_interp_filter, the copy
+ * when lengths are equal), rows first into a width2 x height intermediate, then columns; height2 == height is svt_av1_[highbd_]resize_plane_horizontal.  Any number of
+ * factor-of-two steps and out > in are accepted, as the C accepts them.  src / dst are device pointers (uint8_t samples at bit_depth 8, uint16_t at 10 / 12), descs
+ * is HOST memory.  The intermediate and what a factor-of-two step leaves live in `workspace` (device, svt_hip_resize_workspace_bytes(descs, n, bit_depth) bytes, 256-byte
+ * aligned); the launches are queued on `stream` and the call does not wait.  Reads stay inside width x height of src, writes inside width2 x height2 of dst.
+ * Returns 0, -1 (bit_depth; a NULL pointer; a dimension < 1 or above 65535; a stride below its width; a workspace that is NULL or too small -- nothing is launched or
+ * written then) or SVT_HIP_E_DEVICE.  svt_hip_resize_workspace_bytes returns 0 for arguments the batch would reject. */
+typedef struct SvtHipResizeDesc {
+    const void *src;
+    void       *dst;
+    int32_t     width, height, in_stride;    /* samples */
+    int32_t     width2, height2, out_stride;
+} SvtHipResizeDesc; /* 40 bytes */
+size_t svt_hip_resize_workspace_bytes(const SvtHipResizeDesc *descs, uint32_t n, int bit_depth);
+int    svt_hip_resize_plane_batch(const SvtHipResizeDesc *descs /* host */, uint32_t n, int bit_depth, void *workspace, size_t workspace_bytes, void *stream);
+/* single-call forms with the reference's prototypes: the two dispatch pointers of aom_dsp_rtcd.h:900, :902 (exported, NOT installed by svt_hip_setup_rtcd:
+ * INTEGRATION.md).  Host pointers; upload, the launches above, download.  ACCEPTED RANGE, outside of which EB_ErrorBadParameter is returned and nothing is written:
+ * the conditions of the batched entry; bd 8, 10 or 12 in the highbd form.  EB_ErrorInsufficientResources stands for a device failure.  The four 1-D pointers
+ * (svt_av1_interpolate_core, svt_av1_down2_symeven and their highbd forms) exist inside the kernels only: one row per host round trip would be all latency. */
+#ifdef SVT_HIP_REFERENCE_TYPES
+typedef EbErrorType SvtHipErrorType;
+#else
+typedef int32_t SvtHipErrorType; /* EbErrorType (EbSvtAv1.h:121): an int-sized enum with negative members */
+#endif
+SvtHipErrorType svt_av1_resize_plane_hip(const uint8_t *const input, int height, int width, int in_stride, uint8_t *output, int height2, int width2, int out_stride);
+SvtHipErrorType svt_av1_highbd_resize_plane_hip(const uint16_t *const input, int height, int width, int in_stride, uint16_t *output, int height2, int width2,
+                                                int out_stride, int bd);
+
+/* C. The normative super-resolution upscale, the planes of a picture per call (three per launch): what svt_av1_upscale_normative_rows (super_res.c:214) leaves in
+ * dst, bit for bit -- x_step_qn and x0_qn as super_res.c:43-52, the x0_qn carry from tile column to tile column (:282), the last tile column ending at
+ * upscaled_plane_width, Upscale_Filter of the AV1 specification.  Frame-edge tile columns replicate their edge sample: the C overwrites and restores five border
+ * columns of the SOURCE, the kernel clamps the read to [first tile column's first sample, last tile column's last sample] instead and never writes src; interior
+ * tile-column edges read the real neighbours.  READABLE EXTENT: columns 0 .. (tile_col_start_mi[n_tile_cols] << (2 - sub_x)) - 1 of each of the `rows` rows.
+ * src / dst are device pointers and must not overlap; descs is HOST memory; the launches are queued on `stream` and the call does not wait.
+ * Returns 0, -1 (a NULL pointer; rows or a width < 1 or above 65535; upscaled below downscaled width; a stride below its width or src_stride not above the last
+ * source sample; superres_denom outside 8 .. 16; sub_x above 1; n_tile_cols outside 1 .. 64 or starts that do not rise from 0; bd not 8 / 10 / 12; sample_bytes
+ * not 1 / 2, or 1 with bd above 8; overlapping src and dst -- nothing is launched then) or SVT_HIP_E_DEVICE. */
+typedef struct SvtHipUpscaleDesc {
+    const void *src;
+    void       *dst;
+    int32_t     src_stride, dst_stride, rows; /* samples */
+    int32_t     downscaled_plane_width, upscaled_plane_width; /* already ROUND_POWER_OF_TWO(frame_width / superres_upscaled_width, sub_x) */
+    uint8_t     superres_denom, sub_x;
+    uint8_t     bd;           /* 8 / 10 / 12: the clip */
+    uint8_t     sample_bytes; /* 1, or 2; bd == 8 with 2-byte samples is the 16-bit pipeline and clips to 255 */
+    int32_t     n_tile_cols;
+    int32_t     tile_col_start_mi[65]; /* what svt_av1_tile_set_col yields: mi_col_start of every tile column, then mi_col_end of the last (= mi_cols) */
+} SvtHipUpscaleDesc; /* 304 bytes */
+int svt_hip_superres_upscale_batch(const SvtHipUpscaleDesc *descs /* host */, uint32_t n, void *stream);
+/* The same for one plane in HOST memory, the descriptor's members flattened.  svt_av1_upscale_normative_rows takes an Av1Common * and has no dispatch pointer, so
+ * there is no reference prototype to mirror: this form's argument list is the library's own.  src_stride / dst_stride in samples. */
+int svt_hip_upscale_normative_rows_host(const void *src, int src_stride, void *dst, int dst_stride, int rows, int downscaled_plane_width, int upscaled_plane_width,
+                                        int superres_denom, int sub_x, int n_tile_cols, const int32_t *tile_col_start_mi, int bd, int sample_bytes);
+
 /* ------------------------------------------- block variance family and the MD sub-pel motion search (csrc/mdsubpel.hip) -------------------- */
 /* The AomVarianceFnPtr primitives of svt_aom_mefn_ptr (av1me.c:29-197) for n blocks of mixed sizes in one launch, 8-bit luma.  bsize is a BlockSize 0 .. 21 (the 22
  * sizes of VARIANCES(W, H), variance.c:324-345).  Per block, by kind:
@@ -1642,6 +1731,19 @@ void svt_av1_warp_affine_hip(const int32_t *mat, const uint8_t *ref, int width, 
 void svt_av1_highbd_warp_affine_hip(const int32_t *mat, const uint8_t *ref8b, const uint8_t *ref2b, int width, int height, int stride8b, int stride2b,
                                     uint16_t *pred, int p_col, int p_row, int p_width, int p_height, int p_stride, int subsampling_x, int subsampling_y, int bd,
                                     SvtHipConvolveParams *conv_params, int16_t alpha, int16_t beta, int16_t gamma, int16_t delta);
+/* the two scaled-convolve forms (csrc/scale.hip; common_dsp_rtcd.h: svt_av1_convolve_2d_scale, svt_av1_highbd_convolve_2d_scale; exported, NOT installed by
+ * svt_hip_setup_rtcd: INTEGRATION.md).  Host pointers; the 16 x 8 taps are read from filter_ptr of the caller's InterpFilterParams (taps must be 8; any values) and
+ * conv_params->round_0 / round_1 / is_compound / do_average / use_dist_wtd_comp_avg / fwd_offset / bck_offset / dst / dst_stride are honoured as the C does:
+ * is_compound with do_average == 0 writes the ConvBufType buffer and leaves dst untouched.  Only the rectangle the C reads is copied to the device: columns
+ * -3 .. (((w - 1) * x_step_qn + subpel_x_qn) >> 10) + 4, rows likewise.  ACCEPTED RANGE, outside of which nothing is written: w, h powers of two 2 .. 128; phases
+ * 0 .. 1023; steps 64 .. 2048; the roundings as for the jnt_ forms (0 <= round_0 <= 7, round_1 >= 0, round_0 + round_1 <= 14, round_1 <= 7 when is_compound); bd 10
+ * or 12 in the highbd form. */
+void svt_av1_convolve_2d_scale_hip(const uint8_t *src, int src_stride, uint8_t *dst, int dst_stride, int w, int h, const SvtHipInterpFilterParams *filter_params_x,
+                                   const SvtHipInterpFilterParams *filter_params_y, const int subpel_x_qn, const int x_step_qn, const int subpel_y_qn,
+                                   const int y_step_qn, SvtHipConvolveParams *conv_params);
+void svt_av1_highbd_convolve_2d_scale_hip(const uint16_t *src, int src_stride, uint16_t *dst, int dst_stride, int w, int h,
+                                          const SvtHipInterpFilterParams *filter_params_x, const SvtHipInterpFilterParams *filter_params_y, const int subpel_x_qn,
+                                          const int x_step_qn, const int subpel_y_qn, const int y_step_qn, SvtHipConvolveParams *conv_params, int bd);
 /* the sixteen inter-prediction forms (csrc/interpred.hip; described with svt_hip_inter_pred_batch above) */
 #define SVT_HIP_DECLARE_CONVOLVE(name)                                                                                                                               \
     void svt_av1_##name##_hip(const uint8_t *src, int32_t src_stride, uint8_t *dst, int32_t dst_stride, int32_t w, int32_t h,                                        \

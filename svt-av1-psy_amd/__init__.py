@@ -382,6 +382,30 @@ PROTOTYPES["svt_av1_warp_affine_hip"] = (None, [vp, vp, C.c_int, C.c_int, C.c_in
 PROTOTYPES["svt_av1_highbd_warp_affine_hip"] = (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp] + [C.c_int] * 8 + [vp] + [C.c_int16] * 4)
 
 
+# pictures of another size (csrc/scale.hip): SvtHipScaledPredDesc, SvtHipResizeDesc, SvtHipUpscaleDesc
+SCALE_NO_STEP, SCALE_STEP_MIN, SCALE_STEP_MAX = 1024, 64, 2048  # x_step_q4 / y_step_q4: not scaled, 1:16, 2:1
+ScaledPredDesc = np.dtype([("src_off", "<u8", (2,)), ("dst_off", "<u8"), ("src_stride", "<u4", (2,)), ("dst_stride", "<u4"), ("subpel_x", "<u2", (2,)),
+                           ("subpel_y", "<u2", (2,)), ("xs", "<u2", (2,)), ("ys", "<u2", (2,)), ("plane", "u1", (2,)), ("w", "u1"), ("h", "u1"), ("filter_x", "u1"),
+                           ("filter_y", "u1"), ("compound", "u1"), ("fwd_offset", "u1"), ("bck_offset", "u1"), ("pad", "u1", (3,))])
+ResizeDesc = np.dtype([("src", "<u8"), ("dst", "<u8"), ("width", "<i4"), ("height", "<i4"), ("in_stride", "<i4"), ("width2", "<i4"), ("height2", "<i4"),
+                       ("out_stride", "<i4")])
+UpscaleDesc = np.dtype([("src", "<u8"), ("dst", "<u8"), ("src_stride", "<i4"), ("dst_stride", "<i4"), ("rows", "<i4"), ("downscaled_plane_width", "<i4"),
+                        ("upscaled_plane_width", "<i4"), ("superres_denom", "u1"), ("sub_x", "u1"), ("bd", "u1"), ("sample_bytes", "u1"), ("n_tile_cols", "<i4"),
+                        ("tile_col_start_mi", "<i4", (65,))])
+assert ScaledPredDesc.itemsize == 64 and ResizeDesc.itemsize == 40 and UpscaleDesc.itemsize == 304
+PROTOTYPES["svt_hip_inter_pred_scaled_batch"] = (C.c_int, [InterPredPlanes, vp, vp, C.c_uint32, C.c_int, vp, vp])
+_CS = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]  # src .. h, the two filters, subpel_x, x_step, subpel_y, y_step, conv_params
+PROTOTYPES["svt_av1_convolve_2d_scale_hip"] = (None, _CS)
+PROTOTYPES["svt_av1_highbd_convolve_2d_scale_hip"] = (None, _CS + [C.c_int])
+PROTOTYPES["svt_hip_resize_workspace_bytes"] = (C.c_size_t, [vp, C.c_uint32, C.c_int])
+PROTOTYPES["svt_hip_resize_plane_batch"] = (C.c_int, [vp, C.c_uint32, C.c_int, vp, C.c_size_t, vp])
+_RP = [vp, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int, C.c_int]
+PROTOTYPES["svt_av1_resize_plane_hip"] = (C.c_int32, _RP)
+PROTOTYPES["svt_av1_highbd_resize_plane_hip"] = (C.c_int32, _RP + [C.c_int])
+PROTOTYPES["svt_hip_superres_upscale_batch"] = (C.c_int, [vp, C.c_uint32, vp])
+PROTOTYPES["svt_hip_upscale_normative_rows_host"] = (C.c_int, [vp, C.c_int, vp, C.c_int] + [C.c_int] * 6 + [vp, C.c_int, C.c_int])
+
+
 # block variance family and the MD sub-pel search (csrc/mdsubpel.hip): SvtHipBlockVarDesc, SvtHipBlockVarResult, SvtHipMvCostTable, SvtHipMdSubpelDesc, SvtHipMdSubpelResult
 VAR_VAR, VAR_SUBPIX, VAR_UPSAMPLED, VAR_MSE, VAR_OBMC_SAD, VAR_OBMC_VAR, VAR_OBMC_SUBPIX = range(7)
 MV_VALS = 32767
