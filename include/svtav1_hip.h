@@ -1319,6 +1319,116 @@ int svt_hip_superres_upscale_batch(const SvtHipUpscaleDesc *descs /* host */, ui
 int svt_hip_upscale_normative_rows_host(const void *src, int src_stride, void *dst, int dst_stride, int rows, int downscaled_plane_width, int upscaled_plane_width,
                                         int superres_denom, int sub_x, int n_tile_cols, const int32_t *tile_col_start_mi, int bd, int sample_bytes);
 
+/* ------------------------------------------- AV1 luma palette: k-means, colour search, map cost, prediction (csrc/palette.hip) -------------- */
+/* Everything below is bit-exact with the reference's C (palette.c, k_means_template.h, pic_analysis_process.c:1808-1845, cabac_context_model.c:2458,
+ * enc_intra_prediction.c:501-508, :647-655).  Descriptors live in DEVICE memory, one launch per call, queued on `stream`; the call does not wait.
+ * STATUS, all five batched entries: status != NULL -> status[i] = 0 (done), 1 (invalid descriptor: skipped, nothing of item i written) or 2 (a sample at or above
+ * 1 << bit_depth, see B and C), the call returns 0.  status == NULL -> the descriptors are checked by a small kernel first and the call returns -1 with nothing
+ * launched or written when one is invalid.  Other returns: -1 for a NULL base pointer or a bit depth the entry does not take, SVT_HIP_E_DEVICE.  n == 0 returns 0. */
+
+/* A. svt_av1_k_means_dim1_c / _dim2_c complete for n items: the first assignment, then per iteration centroid sums and counts, DIVIDE_AND_ROUND, the reseed of every
+ * empty cluster in ascending cluster order from one lcg_rand16 stream seeded with (unsigned)data[0], reassignment and the 64-bit total distance; the exit when the
+ * centroids repeat and the exit at max_itr (max_itr <= 0: the first assignment only).  assign_only != 0 is svt_av1_calc_indices_dim1_c / _dim2_c: centroids are
+ * read, never written.  Ties go to the lowest centroid index.  The `this_dist > pre_dist` exit is kept (centroids restored, indices reassigned from them, which is
+ * what pre_indices held); DESIGN 4.26 shows that no input reaches it.  Data values 0 .. 32767 (the C's int arithmetic holds up to there); not checked.
+ * INVALID: dim not 1 / 2, k outside 1 .. 8, n outside 1 .. 16384 (MAX_SB_SQUARE, the C's pre_indices). */
+typedef struct SvtHipKmeansDesc {
+    uint64_t data_off;      /* int32 elements from data_base: n * dim values */
+    uint64_t centroids_off; /* int32 elements from centroids_base: k * dim values, in and out */
+    uint64_t indices_off;   /* bytes from indices_base: n values out */
+    int32_t  n;
+    int32_t  max_itr;
+    uint8_t  dim, k, assign_only;
+    uint8_t  pad[5];
+} SvtHipKmeansDesc; /* 40 bytes */
+int svt_hip_kmeans_batch(const int32_t *data_base, int32_t *centroids_base, uint8_t *indices_base, const SvtHipKmeansDesc *descs, uint32_t n, uint8_t *status,
+                         void *stream);
+
+/* B. svt_av1_count_colors / svt_av1_count_colors_highbd for n blocks of one plane (uint8_t samples at bit_depth 8, uint16_t at 10 / 12): the full histogram
+ * (256 or 1 << bit_depth int32 per block) and n_colors[i] = the number of non-zero bins.  A sample at or above 1 << bit_depth is a caller error: it is not counted
+ * (nothing outside the histogram is read or written), n_colors[i] = 0 as the C returns, status[i] = 2.  INVALID: rows or cols 0. */
+typedef struct SvtHipCountColorsDesc {
+    uint64_t src_off;  /* samples from src_base */
+    uint64_t hist_off; /* int32 elements from hist_base */
+    uint32_t src_stride;
+    uint16_t rows, cols;
+} SvtHipCountColorsDesc; /* 24 bytes */
+int svt_hip_count_colors_batch(const void *src_base, const SvtHipCountColorsDesc *descs, uint32_t n, int bit_depth, int32_t *hist_base, int32_t *n_colors,
+                               uint8_t *status, void *stream);
+
+/* C. search_palette_luma (palette.c:303) whole for n blocks of mixed sizes: the colour count (zero candidates unless 1 < colors <= 64), lb / ub, the min(colors, 8)
+ * dominant colours, the dominant-colour loop (n from min(colors, 8) down to 2 in steps of dominant_color_step), the k-means loop (n down to 2, 50 iterations, the
+ * colors == 2 case) and for each pass palette_rd_y: optimize_palette_colors, the sort with av1_remove_duplicates, the clip, the index map over rows x cols and
+ * extend_palette_color_map to block_width x block_height.  A candidate is kept when its size is above 2, as in the C.  bit_depth 8: uint8_t samples; 10: uint16_t.
+ * OUTPUT of a block, at out_off bytes from out_base: one SvtHipPaletteSearchOut, then 14 index maps map_stride bytes apart.  n_cand is always written; size[s],
+ * colors[s][0 .. size - 1] and the first block_width * block_height bytes of map s only for s < n_cand -- nothing else.  A sample at or above 1 << bit_depth
+ * (16-bit form): n_cand = 0, status 2.  READS rows x cols samples of the source, nothing outside.
+ * INVALID: block_width / block_height not 8, 16, 32 or 64; rows outside 1 .. block_height; cols outside 1 .. block_width; n_cache above 16;
+ * dominant_color_step 0; map_stride below block_width * block_height; an odd out_off. */
+#define SVT_HIP_PALETTE_MAX_CANDS 14
+typedef struct SvtHipPaletteSearchDesc {
+    uint64_t src_off;    /* samples from src_base */
+    uint64_t out_off;    /* bytes from out_base, even */
+    uint32_t src_stride; /* samples */
+    uint32_t map_stride; /* bytes from one candidate's map to the next */
+    uint16_t cache[16];  /* what svt_get_palette_cache_y (svt_hip_palette_cache_y) makes */
+    uint8_t  rows, cols; /* inside the picture */
+    uint8_t  block_width, block_height;
+    uint8_t  n_cache;
+    uint8_t  dominant_color_step;
+    uint8_t  pad[2];
+} SvtHipPaletteSearchDesc; /* 64 bytes */
+typedef struct SvtHipPaletteSearchOut {
+    uint8_t  n_cand; /* 0 .. 14 */
+    uint8_t  size[SVT_HIP_PALETTE_MAX_CANDS];
+    uint8_t  pad;
+    uint16_t colors[SVT_HIP_PALETTE_MAX_CANDS][8];
+} SvtHipPaletteSearchOut; /* 240 bytes; the maps follow */
+int svt_hip_palette_search_luma_batch(const void *src_base, const SvtHipPaletteSearchDesc *descs, uint32_t n, int bit_depth, void *out_base, uint8_t *status,
+                                      void *stream);
+
+/* D. The palette part of the luma mode rate for n (block, candidate) items, three int32 per item in out: map_bits = svt_av1_cost_color_map (every position but
+ * (0, 0) of rows x cols read at pitch block_width, context and reordered index of svt_aom_get_palette_color_index_context_optimized, summed from color_cost =
+ * palette_ycolor_fac_bitss[7][5][8], 280 int32 in device memory), color_bits = svt_av1_palette_color_cost_y (bit_depth is the encoder's), first_bits =
+ * svt_aom_write_uniform_cost(size, map[0]).  map_off / colors_off may point into the output of C in place; rows x block_width bytes of the map are read.  Map entries must be below size (only their low three
+ * bits are used).  INVALID: size outside 2 .. 8; block_width not 8 .. 64 a power of two; rows outside 1 .. 64; cols outside 1 .. block_width; n_cache above 16;
+ * bit_depth not 8 / 10 / 12; an odd colors_off. */
+typedef struct SvtHipPaletteCostDesc {
+    uint64_t map_off;    /* bytes from base */
+    uint64_t colors_off; /* bytes from base, even: `size` uint16_t */
+    uint16_t cache[16];
+    uint8_t  rows, cols, block_width, size, n_cache, bit_depth;
+    uint8_t  pad[2];
+} SvtHipPaletteCostDesc; /* 56 bytes */
+int svt_hip_palette_cost_batch(const void *base, const SvtHipPaletteCostDesc *descs, uint32_t n, const int32_t *color_cost, int32_t *out, uint8_t *status,
+                               void *stream);
+
+/* E. Palette prediction of n transform blocks of mixed sizes: dst[r][c] = colors[map[(r + y) * wpx + c + x]], r < h, c < w.  dst16 == 0: uint8_t destination (the
+ * colour truncated as the C's cast does); dst16 != 0: uint16_t destination, clamped to 0xFF when bit_depth is 8.  INVALID: w / h not 4, 8, 16, 32 or 64; wpx not 8,
+ * 16, 32 or 64; x + w above wpx; y + h above 64; an odd colors_off. */
+typedef struct SvtHipPalettePredDesc {
+    uint64_t map_off;    /* bytes from base */
+    uint64_t colors_off; /* bytes from base, even: 8 uint16_t are readable */
+    uint64_t dst_off;    /* samples from dst_base */
+    uint32_t dst_stride; /* samples */
+    uint8_t  w, h, x, y, wpx;
+    uint8_t  pad[7];
+} SvtHipPalettePredDesc; /* 40 bytes */
+int svt_hip_palette_pred_batch(const void *base, void *dst_base, const SvtHipPalettePredDesc *descs, uint32_t n, int dst16, int bit_depth, uint8_t *status,
+                               void *stream);
+
+/* F. Host pieces.  svt_hip_palette_cache_y is the merge of svt_get_palette_cache_y (palette.c:153): the above and left colour lists (either may be empty; the caller
+ * passes above_n = 0 on a superblock row boundary) into cache[16], returns n_cache; no device work.  The six single-call forms have the reference's prototypes
+ * (aom_dsp_rtcd.h:786-793, palette.c:298-299), take host pointers and are exported, NOT installed by svt_hip_setup_rtcd.  Outside the accepted range of A / B the
+ * k-means forms write nothing and the two counters return 0. */
+int  svt_hip_palette_cache_y(const uint16_t *above_colors, int above_n, const uint16_t *left_colors, int left_n, uint16_t *cache);
+void svt_av1_k_means_dim1_hip(const int *data, int *centroids, uint8_t *indices, int n, int k, int max_itr);
+void svt_av1_k_means_dim2_hip(const int *data, int *centroids, uint8_t *indices, int n, int k, int max_itr);
+void svt_av1_calc_indices_dim1_hip(const int *data, const int *centroids, uint8_t *indices, int n, int k);
+void svt_av1_calc_indices_dim2_hip(const int *data, const int *centroids, uint8_t *indices, int n, int k);
+int  svt_av1_count_colors_hip(const uint8_t *src, int stride, int rows, int cols, int *val_count);
+int  svt_av1_count_colors_highbd_hip(uint16_t *src, int stride, int rows, int cols, int bit_depth, int *val_count);
+
 /* ------------------------------------------- block variance family and the MD sub-pel motion search (csrc/mdsubpel.hip) -------------------- */
 /* The AomVarianceFnPtr primitives of svt_aom_mefn_ptr (av1me.c:29-197) for n blocks of mixed sizes in one launch, 8-bit luma.  bsize is a BlockSize 0 .. 21 (the 22
  * sizes of VARIANCES(W, H), variance.c:324-345).  Per block, by kind:

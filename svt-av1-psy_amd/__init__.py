@@ -406,6 +406,34 @@ PROTOTYPES["svt_hip_superres_upscale_batch"] = (C.c_int, [vp, C.c_uint32, vp])
 PROTOTYPES["svt_hip_upscale_normative_rows_host"] = (C.c_int, [vp, C.c_int, vp, C.c_int] + [C.c_int] * 6 + [vp, C.c_int, C.c_int])
 
 
+# AV1 luma palette (csrc/palette.hip): SvtHipKmeansDesc, SvtHipCountColorsDesc, SvtHipPaletteSearchDesc, SvtHipPaletteSearchOut, SvtHipPaletteCostDesc, SvtHipPalettePredDesc
+PALETTE_MAX_CANDS, PALETTE_MAX_SIZE, PALETTE_MAX_POINTS = 14, 8, 16384
+PALETTE_OK, PALETTE_INVALID, PALETTE_SAMPLE_RANGE = 0, 1, 2  # the status values of the five batched entries
+KmeansDesc = np.dtype([("data_off", "<u8"), ("centroids_off", "<u8"), ("indices_off", "<u8"), ("n", "<i4"), ("max_itr", "<i4"), ("dim", "u1"), ("k", "u1"),
+                       ("assign_only", "u1"), ("pad", "u1", (5,))])
+CountColorsDesc = np.dtype([("src_off", "<u8"), ("hist_off", "<u8"), ("src_stride", "<u4"), ("rows", "<u2"), ("cols", "<u2")])
+PaletteSearchDesc = np.dtype([("src_off", "<u8"), ("out_off", "<u8"), ("src_stride", "<u4"), ("map_stride", "<u4"), ("cache", "<u2", (16,)), ("rows", "u1"), ("cols", "u1"),
+                              ("block_width", "u1"), ("block_height", "u1"), ("n_cache", "u1"), ("dominant_color_step", "u1"), ("pad", "u1", (2,))])
+PaletteSearchOut = np.dtype([("n_cand", "u1"), ("size", "u1", (PALETTE_MAX_CANDS,)), ("pad", "u1"), ("colors", "<u2", (PALETTE_MAX_CANDS, PALETTE_MAX_SIZE))])
+PaletteCostDesc = np.dtype([("map_off", "<u8"), ("colors_off", "<u8"), ("cache", "<u2", (16,)), ("rows", "u1"), ("cols", "u1"), ("block_width", "u1"), ("size", "u1"),
+                            ("n_cache", "u1"), ("bit_depth", "u1"), ("pad", "u1", (2,))])
+PalettePredDesc = np.dtype([("map_off", "<u8"), ("colors_off", "<u8"), ("dst_off", "<u8"), ("dst_stride", "<u4"), ("w", "u1"), ("h", "u1"), ("x", "u1"), ("y", "u1"),
+                            ("wpx", "u1"), ("pad", "u1", (7,))])
+assert KmeansDesc.itemsize == 40 and CountColorsDesc.itemsize == 24 and PaletteSearchDesc.itemsize == 64 and PaletteSearchOut.itemsize == 240
+assert PaletteCostDesc.itemsize == 56 and PalettePredDesc.itemsize == 40
+PROTOTYPES["svt_hip_kmeans_batch"] = (C.c_int, [vp, vp, vp, vp, C.c_uint32, vp, vp])
+PROTOTYPES["svt_hip_count_colors_batch"] = (C.c_int, [vp, vp, C.c_uint32, C.c_int, vp, vp, vp, vp])
+PROTOTYPES["svt_hip_palette_search_luma_batch"] = (C.c_int, [vp, vp, C.c_uint32, C.c_int, vp, vp, vp])
+PROTOTYPES["svt_hip_palette_cost_batch"] = (C.c_int, [vp, vp, C.c_uint32, vp, vp, vp, vp])
+PROTOTYPES["svt_hip_palette_pred_batch"] = (C.c_int, [vp, vp, vp, C.c_uint32, C.c_int, C.c_int, vp, vp])
+PROTOTYPES["svt_hip_palette_cache_y"] = (C.c_int, [vp, C.c_int, vp, C.c_int, vp])
+for _d in (1, 2):
+    PROTOTYPES["svt_av1_k_means_dim%d_hip" % _d] = (None, [vp, vp, vp, C.c_int, C.c_int, C.c_int])
+    PROTOTYPES["svt_av1_calc_indices_dim%d_hip" % _d] = (None, [vp, vp, vp, C.c_int, C.c_int])
+PROTOTYPES["svt_av1_count_colors_hip"] = (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp])
+PROTOTYPES["svt_av1_count_colors_highbd_hip"] = (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp])
+
+
 # block variance family and the MD sub-pel search (csrc/mdsubpel.hip): SvtHipBlockVarDesc, SvtHipBlockVarResult, SvtHipMvCostTable, SvtHipMdSubpelDesc, SvtHipMdSubpelResult
 VAR_VAR, VAR_SUBPIX, VAR_UPSAMPLED, VAR_MSE, VAR_OBMC_SAD, VAR_OBMC_VAR, VAR_OBMC_SUBPIX = range(7)
 MV_VALS = 32767
