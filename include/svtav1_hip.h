@@ -1569,6 +1569,125 @@ void svt_aom_upsampled_pred_hip(void *xd, const void *cm, int mi_row, int mi_col
                                 int subpel_y_q3, const uint8_t *ref, int ref_stride, int subpel_search);
 #endif
 
+/* ------------------------------------------- OBMC motion refinement: weighted target and MV search (csrc/mdsubpel.hip) -------------------- */
+/* A. calc_target_weighted_pred (enc_inter_prediction.c:1756) for n blocks in one launch, 8-bit luma: wsrc and mask of the OBMC error
+ *   error(x, y) = wsrc(x, y) - mask(x, y) * P(x, y), what ctx->wsrc_buf / ctx->mask_buf hold after the call.  Per pixel (row, col), ovA = min(H, 64) >> 1,
+ *   ovL = min(W, 64) >> 1, Mv / Mh = svt_av1_get_obmc_mask(ovA) / (ovL):
+ *     above stage  up_available, col inside an above span, row < ovA:  w = (64 - Mv[row]) * above(row, col), k = Mv[row];  otherwise w = 0, k = 64;
+ *     both times 64;
+ *     left stage   left_available, row inside a left span, col < ovL:  w = (w >> 6) * Mh[col] + (left(row, col) << 6) * (64 - Mh[col]), k = (k >> 6) * Mh[col];
+ *     wsrc = src(row, col) * 4096 - w, mask = k.
+ * A span is what foreach_overlappable_nb_above / _left hand to svt_av1_calc_target_weighted_pred_above_c / _left_c (:1581, :1610): (rel_mi, len_mi) in units of
+ * 4 samples from the block's left / top edge.  The walk over the mi grid (is_neighbor_overlappable, the 4-wide pairing, max_neighbor_obmc, the picture-edge clip)
+ * is the caller's; the spans of one side must not overlap (the walk never produces that).  above / left are the neighbours' predictions with (0, 0) at the block's
+ * top-left sample, the layout svt_hip_inter_pred_batch writes and build_obmc_inter_pred reads: planes.base[above_plane] + above_off + row * above_stride + col.
+ * READABLE EXTENT: W x H of src; of above the spans' columns of rows 0 .. ovA - 1, and only when up_available; of left columns 0 .. ovL - 1 of the spans' rows, and
+ * only when left_available.
+ * Output: W * H contiguous int32_t (pitch W) at wsrc_out + out_off and at mask_out + out_off.
+ * bsize: OBMC needs 8 samples in both directions (is_motion_variation_allowed_bsize), so BlockSize 0, 1, 2, 16, 17 are invalid.
+ * INVALID DESCRIPTORS (such a bsize or one >= 22; more than four spans on a side; a span with len_mi == 0 or rel_mi + len_mi > the block's mi count; a plane index
+ * >= 32, or a plane without a base on a side that is available and has spans; src_base == NULL) never fault: status / return value exactly as
+ * svt_hip_inter_pred_batch; the output of an invalid descriptor is not written. */
+#define SVT_HIP_OBMC_MAX_SPANS 4
+typedef struct SvtHipObmcWsrcDesc {
+    uint64_t src_off;        /* bytes from src_base */
+    uint64_t above_off;      /* samples from planes.base[above_plane] */
+    uint64_t left_off;       /* samples from planes.base[left_plane] */
+    uint64_t out_off;        /* int32_t elements from wsrc_out and from mask_out */
+    uint32_t src_stride, above_stride, left_stride;
+    uint8_t  above_plane, left_plane;
+    uint8_t  bsize;
+    uint8_t  up_available, left_available;
+    uint8_t  n_above, n_left; /* spans per side, 0 .. 4 */
+    uint8_t  pad0;
+    uint8_t  above_rel[SVT_HIP_OBMC_MAX_SPANS], above_len[SVT_HIP_OBMC_MAX_SPANS]; /* rel_mi_col, nb_mi_width */
+    uint8_t  left_rel[SVT_HIP_OBMC_MAX_SPANS], left_len[SVT_HIP_OBMC_MAX_SPANS];   /* rel_mi_row, nb_mi_height */
+    uint8_t  pad[4];
+} SvtHipObmcWsrcDesc; /* 72 bytes */
+int svt_hip_obmc_wsrc_batch(SvtHipInterPredPlanes planes, const uint8_t *src_base, const SvtHipObmcWsrcDesc *descs, uint32_t n, int32_t *wsrc_out, int32_t *mask_out,
+                            uint8_t *status, void *stream);
+/* B. n OBMC motion refinements in one launch: one item is one call of single_motion_search (mode_decision.c:2290) with motion_mode == OBMC_CAUSAL, complete, 8-bit luma:
+ *   full-pel (do_full_refine)  svt_av1_set_mv_search_range(ref_mv) on a copy of the limits; mvp_full = best_pred_mv >> 3 clamped to it;
+ *           obmc_refining_search_sad (av1me.c:721): osdf + mvsad_err_cost at the centre, then up to fpel_search_range rounds of the 4 (fpel_search_diag: 8) neighbours
+ *           {-1,0} {0,-1} {0,1} {1,0} {-1,1} {1,1} {1,-1} {-1,-1} in that order, is_mv_in, strict < against the running best before and after the cost is added, stop
+ *           on a round without a winner; then get_obmc_mvpred_var: thissme = ovf + svt_aom_mv_err_cost(mv * 8).  Without it the start is best_pred_mv >> 3;
+ *   sub-pel (do_frac_refine)   svt_av1_find_best_obmc_sub_pixel_tree_up (av1me.c:963) with set_subpel_mv_search_range on the un-narrowed limits: the centre error,
+ *           round = 3 - forced_stop (2 when !allow_hp && round == 3), per round the four axis candidates, the diagonal from cost_array, the move, and
+ *           SECOND_LEVEL_CHECKS_BEST when iters_per_step > 1 and the round had a winner; INT_MAX for a candidate outside the range; every comparison unsigned.
+ *           subpel_search_type 0: osvf (OBMC_SUBPIX above); 1 .. 3: svt_aom_upsampled_pred with USE_2_TAPS / _4_TAPS / _8_TAPS, then ovf.  Without it the vector is << 3;
+ *   rate    svt_av1_mv_bit_cost with MV_COST_WEIGHT 108, or svt_av1_mv_bit_cost_light.
+ * refine_level of svt_aom_obmc_motion_refinement maps to the two flags as single_motion_search does: 0, 1, 3 -> do_full_refine = do_frac_refine = 1; 2, 4 ->
+ * do_full_refine = 0, do_frac_refine = 1; any other level -> both 0.  The encoder passes forced_stop 0, iters_per_step 2, subpel_search_type 3, fpel_search_range /
+ * fpel_search_diag of obmc_ctrls, sad_per_bit = svt_aom_get_sad_per_bit(base_q_idx, 0), error_per_bit = max(full_lambda_md[8 bit] >> RD_EPB_SHIFT, 1).
+ * Costs: approx_inter_rate selects mvsad_err_cost_light / svt_aom_mv_err_cost_light / svt_av1_mv_bit_cost_light (1296 + 50 * the differences' magnitudes, the full-pel
+ * ones times 8); otherwise tables[cost_table] as in the sub-pel search above (svt_mv_cost's clip and the table-end rule; the differences narrowed to int16_t as MV
+ * does; (unsigned)cost * sad_per_bit rounded by 9 bits at full-pel, (int64_t)cost * error_per_bit rounded by 14 bits at sub-pel).  cost_table < 0 or tables == NULL is
+ * mvcost == NULL: every table cost is 0 (the C tests the pointer in svt_aom_mv_err_cost only; here the full-pel cost and the rate follow it).
+ * THE TARGET, per item: SVT_HIP_OBMC_TARGET_ARRAYS -- W * H int32_t at wsrc_base + wsrc_off and mask_base + mask_off, any values svt_hip_block_var_batch accepts;
+ * SVT_HIP_OBMC_TARGET_DERIVED -- the inputs of A (source, the two neighbour predictions, availability, spans): the wave computes wsrc / mask from those bytes with the
+ * closed form of A each time it needs them and the int32_t arrays never exist in memory.  Both forms give identical results for the arrays A produces.
+ * A candidate's error is by definition what svt_hip_block_var_batch returns for the same (pre, wsrc, mask) with kind OBMC_SAD, OBMC_VAR, OBMC_SUBPIX, or UPSAMPLED
+ * prediction followed by OBMC_VAR; readable extents of the reference are those of these kinds at every candidate visited.  No vector is clamped to a picture: the
+ * limits (full-pel units: the UMV window of svt_hip_obmc_mv_limits) and the padding are the caller's.
+ * Result: mv (1/8 sample), the full-pel winner, thissme (0 without full-pel), besterr / distortion / sse1 of the sub-pel search (0 without it; sse1 of a caller that
+ * set it to 0), rate_mv, fp_rounds = full-pel rounds that moved the centre, evals = predictions compared with the target (a measurement aid).
+ * INVALID DESCRIPTORS (a bsize A rejects; target_form > 1; subpel_search_type > 3; forced_stop > 3; fpel_search_range > 64; cost_table >= n_tables; a plane index >= 32
+ * or a reference plane without a base; ARRAYS without wsrc_base / mask_base; DERIVED with what A rejects) never fault: status / return value exactly as
+ * svt_hip_inter_pred_batch; the result of an invalid descriptor is not written. */
+#define SVT_HIP_OBMC_TARGET_ARRAYS  0
+#define SVT_HIP_OBMC_TARGET_DERIVED 1
+typedef struct SvtHipObmcSearchDesc {
+    uint64_t ref_off;        /* samples from planes.base[ref_plane]: the block's position in the reference (vector 0, 0) */
+    uint64_t wsrc_off, mask_off;          /* ARRAYS: int32_t elements from wsrc_base / mask_base */
+    uint64_t src_off, above_off, left_off; /* DERIVED: as in SvtHipObmcWsrcDesc */
+    uint32_t ref_stride, src_stride, above_stride, left_stride;
+    int32_t  lim_col_min, lim_col_max, lim_row_min, lim_row_max; /* x->mv_limits of mode_decision.c:2324-2327, full-pel (svt_hip_obmc_mv_limits) */
+    int32_t  sad_per_bit, error_per_bit;
+    int32_t  cost_table;     /* index into tables, < 0: none */
+    int16_t  best_pred_mv_row, best_pred_mv_col; /* 1/8 sample */
+    int16_t  ref_mv_row, ref_mv_col;
+    uint8_t  ref_plane, above_plane, left_plane;
+    uint8_t  bsize;
+    uint8_t  target_form;    /* SVT_HIP_OBMC_TARGET_* */
+    uint8_t  do_full_refine, do_frac_refine;
+    uint8_t  approx_inter_rate;
+    uint8_t  fpel_search_range; /* 0 .. 64 */
+    uint8_t  fpel_search_diag;
+    uint8_t  allow_hp;
+    uint8_t  forced_stop;    /* 0 .. 3 */
+    uint8_t  iters_per_step;
+    uint8_t  subpel_search_type; /* 0 bilinear osvf, 1 .. 3 USE_2_TAPS / USE_4_TAPS / USE_8_TAPS */
+    uint8_t  up_available, left_available;
+    uint8_t  n_above, n_left;
+    uint8_t  pad0[2];
+    uint8_t  above_rel[SVT_HIP_OBMC_MAX_SPANS], above_len[SVT_HIP_OBMC_MAX_SPANS];
+    uint8_t  left_rel[SVT_HIP_OBMC_MAX_SPANS], left_len[SVT_HIP_OBMC_MAX_SPANS];
+} SvtHipObmcSearchDesc; /* 136 bytes */
+typedef struct SvtHipObmcSearchResult {
+    int16_t  mv_row, mv_col; /* x->best_mv, 1/8 sample */
+    int16_t  fp_row, fp_col; /* the full-pel vector the sub-pel search started from */
+    int32_t  thissme;        /* what svt_av1_obmc_full_pixel_search returns */
+    uint32_t besterr;        /* what svt_av1_find_best_obmc_sub_pixel_tree_up returns */
+    int32_t  distortion;
+    uint32_t sse1;
+    int32_t  rate_mv;
+    uint32_t fp_rounds;
+    uint32_t evals;
+} SvtHipObmcSearchResult; /* 36 bytes */
+int svt_hip_obmc_search_batch(SvtHipInterPredPlanes planes, const uint8_t *src_base, const int32_t *wsrc_base, const int32_t *mask_base, const SvtHipMvCostTable *tables,
+                              uint32_t n_tables, const SvtHipObmcSearchDesc *descs, uint32_t n, SvtHipObmcSearchResult *out, uint8_t *status, void *stream);
+/* Host helper: the UMV window single_motion_search sets (:2324-2327), full-pel: limits = col_min, col_max, row_min, row_max.  Returns 0, or -1 (nothing written) for
+ * bsize outside 0 .. 21 or a NULL limits. */
+int svt_hip_obmc_mv_limits(int mi_row, int mi_col, int bsize, int mi_rows, int mi_cols, int32_t *limits);
+/* One item from host memory: upload, one launch, download.  desc gives everything but the addresses: its offsets, strides and plane indices are ignored.
+ * ref points at the block's position in the reference; ref_border samples around the W x H block are readable on every side, and the call returns -1 without
+ * launching when |start vector| + fpel_search_range (with full-pel) + 6 (with sub-pel: under two samples of movement and the four of the filter) exceeds it.  ARRAYS: wsrc / mask (W * H each); DERIVED: src, above, left with
+ * their strides (above / left may be NULL on a side that is not available or has no span).  table: one SvtHipMvCostTable or NULL (desc->cost_table is ignored).
+ * Returns 0 and writes *result; -1 for an invalid item or a NULL pointer, SVT_HIP_E_DEVICE on a device error: nothing is written then. */
+int svt_hip_obmc_refine_host(const SvtHipObmcSearchDesc *desc, const uint8_t *ref, int ref_stride, int ref_border, const int32_t *wsrc, const int32_t *mask,
+                             const uint8_t *src, int src_stride, const uint8_t *above, int above_stride, const uint8_t *left, int left_stride,
+                             const SvtHipMvCostTable *table, SvtHipObmcSearchResult *result);
+
 /* ------------------------------------------- picture-analysis statistics and the variance boost (csrc/picstats.hip) ------------------------- */
 #define SVT_HIP_BLOCK_MEAN_PREC_FULL 0 /* BLOCK_MEAN_PREC_FULL / _SUB, definitions.h:2391-2392 */
 #define SVT_HIP_BLOCK_MEAN_PREC_SUB  1

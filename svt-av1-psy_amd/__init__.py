@@ -465,6 +465,29 @@ for _w, _h in VARIANCE_SIZES:
 PROTOTYPES["svt_aom_mse16x16_hip"] = (C.c_uint32, [vp, C.c_int32, vp, C.c_int32, vp])
 PROTOTYPES["svt_aom_upsampled_pred_hip"] = (None, [vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, C.c_int])
 
+# OBMC motion refinement (csrc/mdsubpel.hip): SvtHipObmcWsrcDesc, SvtHipObmcSearchDesc, SvtHipObmcSearchResult
+OBMC_MAX_SPANS = 4
+OBMC_TARGET_ARRAYS, OBMC_TARGET_DERIVED = 0, 1
+_OBMC_SPANS = [("above_rel", "u1", (4,)), ("above_len", "u1", (4,)), ("left_rel", "u1", (4,)), ("left_len", "u1", (4,))]
+ObmcWsrcDesc = np.dtype([("src_off", "<u8"), ("above_off", "<u8"), ("left_off", "<u8"), ("out_off", "<u8"), ("src_stride", "<u4"), ("above_stride", "<u4"),
+                         ("left_stride", "<u4"), ("above_plane", "u1"), ("left_plane", "u1"), ("bsize", "u1"), ("up_available", "u1"), ("left_available", "u1"),
+                         ("n_above", "u1"), ("n_left", "u1"), ("pad0", "u1")] + _OBMC_SPANS + [("pad", "u1", (4,))])
+ObmcSearchDesc = np.dtype([("ref_off", "<u8"), ("wsrc_off", "<u8"), ("mask_off", "<u8"), ("src_off", "<u8"), ("above_off", "<u8"), ("left_off", "<u8"),
+                           ("ref_stride", "<u4"), ("src_stride", "<u4"), ("above_stride", "<u4"), ("left_stride", "<u4"), ("lim_col_min", "<i4"), ("lim_col_max", "<i4"),
+                           ("lim_row_min", "<i4"), ("lim_row_max", "<i4"), ("sad_per_bit", "<i4"), ("error_per_bit", "<i4"), ("cost_table", "<i4"),
+                           ("best_pred_mv_row", "<i2"), ("best_pred_mv_col", "<i2"), ("ref_mv_row", "<i2"), ("ref_mv_col", "<i2"), ("ref_plane", "u1"),
+                           ("above_plane", "u1"), ("left_plane", "u1"), ("bsize", "u1"), ("target_form", "u1"), ("do_full_refine", "u1"), ("do_frac_refine", "u1"),
+                           ("approx_inter_rate", "u1"), ("fpel_search_range", "u1"), ("fpel_search_diag", "u1"), ("allow_hp", "u1"), ("forced_stop", "u1"),
+                           ("iters_per_step", "u1"), ("subpel_search_type", "u1"), ("up_available", "u1"), ("left_available", "u1"), ("n_above", "u1"), ("n_left", "u1"),
+                           ("pad0", "u1", (2,))] + _OBMC_SPANS)
+ObmcSearchResult = np.dtype([("mv_row", "<i2"), ("mv_col", "<i2"), ("fp_row", "<i2"), ("fp_col", "<i2"), ("thissme", "<i4"), ("besterr", "<u4"), ("distortion", "<i4"),
+                             ("sse1", "<u4"), ("rate_mv", "<i4"), ("fp_rounds", "<u4"), ("evals", "<u4")])
+assert ObmcWsrcDesc.itemsize == 72 and ObmcSearchDesc.itemsize == 136 and ObmcSearchResult.itemsize == 36
+PROTOTYPES["svt_hip_obmc_wsrc_batch"] = (C.c_int, [InterPredPlanes, vp, vp, C.c_uint32, vp, vp, vp, vp])
+PROTOTYPES["svt_hip_obmc_search_batch"] = (C.c_int, [InterPredPlanes, vp, vp, vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp, vp])
+PROTOTYPES["svt_hip_obmc_mv_limits"] = (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp])
+PROTOTYPES["svt_hip_obmc_refine_host"] = (C.c_int, [vp, vp, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, C.c_int, vp, C.c_int, vp, vp])
+
 
 # picture-analysis statistics and the variance boost (csrc/picstats.hip): SvtHipVarBoostFrame
 BLOCK_MEAN_PREC_FULL, BLOCK_MEAN_PREC_SUB = 0, 1

@@ -4,7 +4,9 @@
 //  * block_var_kernel: one launch, n descriptors of mixed sizes and kinds: svt_aom_variance / sub_pixel_variance / obmc_sad / obmc_variance / obmc_sub_pixel_variance
 //    {W}x{H}_c (C_DEFAULT/variance.c, sad_av1.c), svt_aom_mse16x16_c (svt_psnr.c:63) and svt_aom_upsampled_pred_c + vf (what svt_upsampled_pref_error computes).
 //  * md_subpel_kernel: one launch, n (block, reference) searches: svt_av1_find_best_sub_pixel_tree / _tree_pruned (mcomp.c:688, :606) as md_subpel_search calls them.
-//  Both follow tf_subpel.hip: ONE WAVE per item; the candidate loop is sequential and wave-uniform -- a step counter names the next candidate, so that there is one
+//  * obmc_wsrc_kernel / obmc_search_kernel: the OBMC motion refinement on top of the OBMC kinds -- calc_target_weighted_pred (enc_inter_prediction.c:1756) for n blocks and
+//    single_motion_search (mode_decision.c:2290) for n OBMC_CAUSAL candidates; DESIGN.md 4.27.  They sit here for pred_full / pred_bil / pred_up / wave_sum.
+//  Both searches and the primitives follow tf_subpel.hip: ONE WAVE per item; the candidate loop is sequential and wave-uniform -- a step counter names the next candidate, so that there is one
 //  evaluation site; the 64 lanes split the block's pixels (pixel i = lane + 64 k, row-major); sum / sse are wave reductions made uniform with v_readfirstlane, accept
 //  and exit decisions are scalar.  The source block is read once per item into the wave's LDS slice; the horizontally filtered intermediate of the 2-D upsampled
 //  prediction ((H + 7) rows x W, uint8_t as in the C) lives behind it, COLUMN-major with a pitch of H + 8, so that the vertical stage reads a lane's eight values
@@ -446,6 +448,364 @@ __global__ __launch_bounds__(256) void md_subpel_check_kernel(const SvtHipInterP
     if (bad) *bad_out = 1;
 }
 
+// ---- OBMC motion refinement ------------------------------------------------------------------------------------------------------------
+// obmc_mask_1 .. obmc_mask_32 (inter_prediction.c:2407-2417) back to back: the mask of length n starts at n - 1 (svt_av1_get_obmc_mask)
+__device__ constexpr uint8_t kObmcMask[63] = {64, 45, 64, 39, 50, 59, 64, 36, 42, 48, 53, 57, 61, 64, 64, 34, 37, 40, 43, 46, 49, 52, 54, 56, 58, 60, 61, 64, 64, 64, 64,
+                                              33, 35, 36, 38, 40, 41, 43, 44, 45, 47, 48, 50, 51, 52, 53, 55, 56, 57, 58, 59, 60, 60, 61, 62, 64, 64, 64, 64, 64, 64, 64, 64};
+constexpr int NB_SMALL = 2048; // bytes of one neighbour prediction's overlap region in LDS: W * ovA resp. H * ovL <= npix / 2
+constexpr int NB_BIG   = 4096; // 128 x 32
+constexpr int OBMC_WEIGHTS   = 256;  // the two 1-D weight rows of a derived target: up to 128 bytes each
+constexpr int OBMC_LDS_SMALL = SMALL_WAVES * (SMALL_PIX + 2 * NB_SMALL + OBMC_WEIGHTS + IM_SMALL); // 52 224 B per workgroup of four waves
+constexpr int OBMC_LDS_BIG   = SRC_BIG + 2 * NB_BIG + OBMC_WEIGHTS + IM_BIG;                       // 42 240 B per one-wave workgroup
+
+// the spans of SvtHipObmcWsrcDesc / SvtHipObmcSearchDesc (same member names)
+template <typename D> __device__ __forceinline__ bool obmc_spans_ok(const D& d, const SvtHipInterPredPlanes& planes) {
+    if (d.bsize >= 22 || kBw[d.bsize] < 8 || kBh[d.bsize] < 8) return false;
+    if (d.n_above > SVT_HIP_OBMC_MAX_SPANS || d.n_left > SVT_HIP_OBMC_MAX_SPANS || d.above_plane >= 32 || d.left_plane >= 32) return false;
+    const int n4w = kBw[d.bsize] >> 2, n4h = kBh[d.bsize] >> 2;
+#pragma unroll
+    for (int k = 0; k < SVT_HIP_OBMC_MAX_SPANS; k++) {
+        if (k < d.n_above && (d.above_len[k] == 0 || (int)d.above_rel[k] + (int)d.above_len[k] > n4w)) return false;
+        if (k < d.n_left && (d.left_len[k] == 0 || (int)d.left_rel[k] + (int)d.left_len[k] > n4h)) return false;
+    }
+    if (d.up_available && d.n_above && planes.base[d.above_plane] == nullptr) return false;
+    if (d.left_available && d.n_left && planes.base[d.left_plane] == nullptr) return false;
+    return true;
+}
+struct ObmcSides {
+    uint32_t amask, lmask; // bit m: mi column / row m of the block lies in an above / left span of an available side
+    int      ovA, ovL;
+};
+template <typename D> __device__ __forceinline__ ObmcSides obmc_sides(const D& d, const int W, const int H) {
+    ObmcSides s;
+    s.amask = s.lmask = 0;
+    s.ovA = std::min(H, 64) >> 1, s.ovL = std::min(W, 64) >> 1;
+#pragma unroll
+    for (int k = 0; k < SVT_HIP_OBMC_MAX_SPANS; k++) {
+        if (d.up_available && k < d.n_above) s.amask |= (uint32_t)((1ull << d.above_len[k]) - 1ull) << d.above_rel[k];
+        if (d.left_available && k < d.n_left) s.lmask |= (uint32_t)((1ull << d.left_len[k]) - 1ull) << d.left_rel[k];
+    }
+    return s;
+}
+// calc_target_weighted_pred (enc_inter_prediction.c:1756) for one pixel: the above callback (:1581), both times 64, the left callback (:1610), the source
+__device__ __forceinline__ void obmc_target(const int s, const int a, const int lf, const bool in_a, const bool in_l, const int mv, const int mh, int& w, int& k) {
+    w = 0, k = 64;
+    if (in_a) w = (64 - mv) * a, k = mv;
+    w *= 64, k *= 64;
+    if (in_l) w = (w >> 6) * mh + (lf << 6) * (64 - mh), k = (k >> 6) * mh;
+    w = s * 4096 - w;
+}
+// one workgroup per item, its 256 threads split the pixels; every pixel is independent
+__global__ __launch_bounds__(256) void obmc_wsrc_kernel(const SvtHipInterPredPlanes planes, const uint8_t* __restrict__ src_base, const SvtHipObmcWsrcDesc* __restrict__ descs,
+                                                        const uint32_t n, int32_t* __restrict__ wsrc_out, int32_t* __restrict__ mask_out, uint8_t* __restrict__ status) {
+    const uint32_t item = blockIdx.x;
+    if (item >= n) return;
+    const SvtHipObmcWsrcDesc d  = descs[item];
+    const bool               ok = obmc_spans_ok(d, planes);
+    if (status && threadIdx.x == 0) status[item] = ok ? 0 : 1;
+    if (!ok) return;
+    const Geo       g  = geo_of(d.bsize);
+    const ObmcSides sd = obmc_sides(d, g.W, g.H);
+    const uint8_t*  src   = src_base + d.src_off;
+    const uint8_t*  above = (const uint8_t*)planes.base[d.above_plane] + d.above_off;
+    const uint8_t*  left  = (const uint8_t*)planes.base[d.left_plane] + d.left_off;
+    int32_t*        ow = wsrc_out + d.out_off;
+    int32_t*        om = mask_out + d.out_off;
+    for (int i = (int)threadIdx.x; i < g.npix; i += 256) {
+        const int  row = i >> g.lw, col = i & (g.W - 1);
+        const bool in_a = row < sd.ovA && ((sd.amask >> (col >> 2)) & 1u), in_l = col < sd.ovL && ((sd.lmask >> (row >> 2)) & 1u);
+        const int  a  = in_a ? load_px(above + (uint32_t)row * d.above_stride + (uint32_t)col) : 0;
+        const int  lf = in_l ? load_px(left + (uint32_t)row * d.left_stride + (uint32_t)col) : 0;
+        int        w, k;
+        obmc_target(load_px(src + (uint32_t)row * d.src_stride + (uint32_t)col), a, lf, in_a, in_l, in_a ? kObmcMask[sd.ovA - 1 + row] : 0,
+                    in_l ? kObmcMask[sd.ovL - 1 + col] : 0, w, k);
+        ow[i] = w, om[i] = k;
+    }
+}
+__global__ __launch_bounds__(256) void obmc_wsrc_check_kernel(const SvtHipInterPredPlanes planes, const SvtHipObmcWsrcDesc* __restrict__ descs, const uint32_t n,
+                                                              uint32_t* __restrict__ bad_out) {
+    bool bad = false;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) bad |= !obmc_spans_ok(descs[i], planes);
+    if (bad) *bad_out = 1;
+}
+
+__device__ __forceinline__ bool obmc_search_desc_ok(const SvtHipObmcSearchDesc& d, const SvtHipInterPredPlanes& planes, const bool have_src, const bool have_arrays,
+                                                    const bool have_tables, const uint32_t n_tables) {
+    if (d.bsize >= 22 || kBw[d.bsize] < 8 || kBh[d.bsize] < 8) return false;
+    if (d.target_form > SVT_HIP_OBMC_TARGET_DERIVED || d.subpel_search_type > 3 || d.forced_stop > 3 || d.fpel_search_range > 64) return false;
+    if (d.ref_plane >= 32 || planes.base[d.ref_plane] == nullptr) return false;
+    if (have_tables && d.cost_table >= 0 && (uint32_t)d.cost_table >= n_tables) return false;
+    if (d.target_form == SVT_HIP_OBMC_TARGET_ARRAYS) return have_arrays;
+    return have_src && obmc_spans_ok(d, planes);
+}
+// One wave per item, as md_subpel_kernel: candidates in the C's order, one after the other and wave-uniform; the lanes split the pixels; every decision is scalar.
+// ARRAYS: wsrc / mask are re-read from memory (L2) by every candidate, as block_var_kernel reads them -- 8 bytes per pixel do not fit the wave's LDS share at the
+// sizes that matter.  DERIVED: the source block and the two overlap regions sit in the wave's LDS slice as bytes and a pixel's (wsrc, mask) is recomputed from them
+// wherever it is used.  The slice: source | above overlap (pitch W) | left overlap (pitch ovL) | the two 1-D weight rows | the intermediate of pred_up.
+template <bool BIG>
+__global__ __launch_bounds__(BIG ? 64 : 64 * SMALL_WAVES) void obmc_search_kernel(const SvtHipInterPredPlanes planes, const uint8_t* __restrict__ src_base,
+                                                                                  const int32_t* __restrict__ wsrc_base, const int32_t* __restrict__ mask_base,
+                                                                                  const SvtHipMvCostTable* __restrict__ tables, const uint32_t n_tables,
+                                                                                  const SvtHipObmcSearchDesc* __restrict__ descs, const uint32_t n,
+                                                                                  SvtHipObmcSearchResult* __restrict__ out, uint8_t* __restrict__ status) {
+    HIP_DYNAMIC_SHARED(uint32_t, smem)
+    constexpr int  WV = BIG ? 1 : SMALL_WAVES, SRCB = BIG ? SRC_BIG : SMALL_PIX, NBB = BIG ? NB_BIG : NB_SMALL, SLICE = SRCB + 2 * NBB + OBMC_WEIGHTS + (BIG ? IM_BIG : IM_SMALL);
+    const int      l = threadIdx.x & 63, wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t item = blockIdx.x * WV + (uint32_t)wv;
+    if (item >= n) return;
+    const SvtHipObmcSearchDesc d  = descs[item];
+    const bool                 ok = obmc_search_desc_ok(d, planes, src_base != nullptr, wsrc_base != nullptr && mask_base != nullptr, tables != nullptr, n_tables);
+    if (status && !BIG && l == 0) status[item] = ok ? 0 : 1;
+    if (!ok) return;
+    const Geo g = geo_of(d.bsize);
+    if ((g.npix > SMALL_PIX) != BIG) return;
+    uint8_t*       srcl = (uint8_t*)smem + wv * SLICE;
+    uint8_t*       abv  = srcl + SRCB;
+    uint8_t*       lft  = abv + NBB;
+    uint8_t*       wrow = lft + NBB; // Mv[row], 64 from row ovA on
+    uint8_t*       wcol = wrow + OBMC_WEIGHTS / 2; // Mh[col], 64 from column ovL on
+    uint8_t*       im   = wcol + OBMC_WEIGHTS / 2;
+    const uint8_t* ref  = (const uint8_t*)planes.base[d.ref_plane] + d.ref_off;
+    const int64_t  rs   = (int64_t)d.ref_stride;
+    const bool     derived = d.target_form == SVT_HIP_OBMC_TARGET_DERIVED;
+    const int32_t* ws   = wsrc_base + (derived ? 0 : d.wsrc_off);
+    const int32_t* mk   = mask_base + (derived ? 0 : d.mask_off);
+    ObmcSides      sd;
+    sd.amask = sd.lmask = 0, sd.ovA = sd.ovL = 0;
+    if (derived) {
+        sd = obmc_sides(d, g.W, g.H);
+        const uint8_t* src = src_base + d.src_off;
+        for (int i = l; i < g.npix; i += 64) srcl[i] = (uint8_t)load_px(src + (uint32_t)(i >> g.lw) * d.src_stride + (uint32_t)(i & (g.W - 1)));
+        for (int i = l; i < g.H; i += 64) wrow[i] = i < sd.ovA ? kObmcMask[sd.ovA - 1 + i] : (uint8_t)64;
+        for (int i = l; i < g.W; i += 64) wcol[i] = i < sd.ovL ? kObmcMask[sd.ovL - 1 + i] : (uint8_t)64;
+        if (sd.amask) {
+            const uint8_t* above = (const uint8_t*)planes.base[d.above_plane] + d.above_off;
+            for (int i = l; i < g.W * sd.ovA; i += 64) {
+                const int row = i >> g.lw, col = i & (g.W - 1);
+                if ((sd.amask >> (col >> 2)) & 1u) abv[i] = (uint8_t)load_px(above + (uint32_t)row * d.above_stride + (uint32_t)col);
+            }
+        }
+        if (sd.lmask) {
+            const uint8_t* left = (const uint8_t*)planes.base[d.left_plane] + d.left_off;
+            const int      lo   = 31 - __clz((unsigned)sd.ovL);
+            for (int i = l; i < g.H * sd.ovL; i += 64) {
+                const int row = i >> lo, col = i & (sd.ovL - 1);
+                if ((sd.lmask >> (row >> 2)) & 1u) lft[i] = (uint8_t)load_px(left + (uint32_t)row * d.left_stride + (uint32_t)col);
+            }
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    const SvtHipMvCostTable* tab = (tables != nullptr && d.cost_table >= 0) ? tables + d.cost_table : nullptr;
+    const int                rr = d.ref_mv_row, rc = d.ref_mv_col;
+    // svt_mv_cost on a difference that is an MV, i.e. int16_t
+    const auto tab_cost = [&](const int16_t dr, const int16_t dc) -> int {
+        const int  j  = dr == 0 ? (dc == 0 ? 0 : 1) : (dc == 0 ? 2 : 3); // svt_av1_get_mv_joint
+        const auto at = [](const int v) {
+            const int k = MV_MAX_ + (v < -MV_UPP_ ? -MV_UPP_ : (v > MV_UPP_ ? MV_UPP_ : v));
+            return k < 0 ? 0 : (k > SVT_HIP_MV_VALS - 1 ? SVT_HIP_MV_VALS - 1 : k);
+        };
+        return (int)((uint32_t)tab->joint[j] + (uint32_t)tab->comp[0][at(dr)] + (uint32_t)tab->comp[1][at(dc)]);
+    };
+    const auto light = [](const int a, const int b) { return 1296u + 50u * ((uint32_t)a + (uint32_t)b); };
+    const int  fcr = rr >> 3, fcc = rc >> 3; // fcenter_mv
+    const auto sad_cost = [&](const int r, const int c) -> uint32_t { // mvsad_err_cost (av1me.c:254), full-pel vectors
+        if (d.approx_inter_rate) return light(abs(c - fcc) * 8, abs(r - fcr) * 8);
+        if (!tab) return 0;
+        return ((uint32_t)tab_cost((int16_t)((r - fcr) * 8), (int16_t)((c - fcc) * 8)) * (uint32_t)d.sad_per_bit + 256u) >> 9;
+    };
+    const auto err_cost = [&](const int16_t r, const int16_t c) -> uint32_t { // svt_aom_mv_err_cost / _light (av1me.c:229, :244)
+        if (d.approx_inter_rate) return light(abs((int)c - rc), abs((int)r - rr));
+        if (!tab) return 0;
+        return (uint32_t)(int)(((int64_t)tab_cost((int16_t)(r - rr), (int16_t)(c - rc)) * d.error_per_bit + 8192) >> 14);
+    };
+    int        sum_l;
+    uint32_t   sse_l, sad_l;
+    // pixel i's (wsrc, mask).  Derived: the closed form of obmc_target without a branch -- a stage that does not apply has the weight 64, under which its neighbour
+    // sample (whatever byte of the slice the index then names) is multiplied by 0: w = (64 - ka) * above * kl + (left << 6) * (64 - kl), k = ka * kl.
+    const auto target = [&](const int i, int& w, int& k) {
+        if (derived) {
+            const int row = i >> g.lw, col = i & (g.W - 1);
+            const int ka = ((sd.amask >> (col >> 2)) & 1u) ? (int)wrow[row] : 64, kl = ((sd.lmask >> (row >> 2)) & 1u) ? (int)wcol[col] : 64;
+            w = (int)srcl[i] * 4096 - ((64 - ka) * (int)abv[i] * kl + ((int)lft[row * sd.ovL + col] << 6) * (64 - kl));
+            k = ka * kl;
+        } else w = ws[i], k = mk[i];
+    };
+    const auto acc = [&](const int i, const int px) { // obmc_variance (variance.c:347) / obmc_sad (sad_av1.c:18), as block_var_kernel
+        int w, k;
+        target(i, w, k);
+        const int      v = (int)((uint32_t)w - (uint32_t)px * (uint32_t)k);
+        const uint32_t r = ((v < 0 ? 0u - (uint32_t)v : (uint32_t)v) + 2048u) >> 12;
+        sad_l += r;
+        sum_l += v < 0 ? -(int)r : (int)r;
+        sse_l += r * r;
+    };
+    const auto reset = [&]() { sum_l = 0, sse_l = 0, sad_l = 0; };
+    const auto finish = [&](uint32_t& sse) {
+        const int sum = wave_sum(sum_l);
+        sse           = (uint32_t)wave_sum((int)sse_l);
+        return variance_of(sse, sum, g.ln);
+    };
+    const auto at_fp = [&](const int r, const int c) { return ref + (int64_t)r * rs + c; }; // get_buf_from_mv
+
+    int16_t  fr = (int16_t)(d.best_pred_mv_row >> 3), fc = (int16_t)(d.best_pred_mv_col >> 3);
+    uint32_t evals = 0, fp_rounds = 0, sse;
+    int      thissme = 0;
+    if (d.do_full_refine) {
+        // svt_av1_set_mv_search_range (av1me.c:205) on a copy of the limits: MAX_FULL_PEL_VAL 1023
+        const int cmin = std::max(d.lim_col_min, std::max((rc >> 3) - 1023 + ((rc & 7) ? 1 : 0), (-MV_UPP_ >> 3) + 1));
+        const int rmin = std::max(d.lim_row_min, std::max((rr >> 3) - 1023 + ((rr & 7) ? 1 : 0), (-MV_UPP_ >> 3) + 1));
+        const int cmax = std::min(d.lim_col_max, std::min((rc >> 3) + 1023, (MV_UPP_ >> 3) - 1));
+        const int rmax = std::min(d.lim_row_max, std::min((rr >> 3) + 1023, (MV_UPP_ >> 3) - 1));
+        fc = (int16_t)((int)fc < cmin ? cmin : ((int)fc > cmax ? cmax : (int)fc)); // clamp_mv
+        fr = (int16_t)((int)fr < rmin ? rmin : ((int)fr > rmax ? rmax : (int)fr));
+        // obmc_refining_search_sad (av1me.c:721).  The neighbours of a round, {-1,0} {0,-1} {0,1} {1,0} {-1,1} {1,1} {1,-1} {-1,-1}, are independent given the running
+        // best: their SADs come from ONE pass over the pixels -- a pixel's (wsrc, mask) is fetched or derived once and meets up to eight samples of the
+        // (W + 2) x (H + 2) window around the centre -- and the C's decisions then run over the eight sums in its order.  A neighbour is_mv_in rejects is not read.
+        constexpr int NR[8] = {-1, 0, 0, 1, -1, 1, 1, -1}, NC[8] = {0, -1, 1, 0, 1, 1, -1, -1};
+        reset();
+        pred_full(at_fp(fr, fc), rs, g, l, acc);
+        evals++;
+        uint32_t  best_sad = (uint32_t)wave_sum((int)sad_l) + sad_cost(fr, fc);
+        const int nn = d.fpel_search_diag ? 8 : 4;
+#pragma unroll 1
+        for (int i = 0; i < (int)d.fpel_search_range; i++) {
+            uint32_t in = 0;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                const int16_t r = (int16_t)(fr + NR[j]), c = (int16_t)(fc + NC[j]);
+                if (j < nn && c >= cmin && c <= cmax && r >= rmin && r <= rmax) in |= 1u << j; // is_mv_in
+            }
+            uint32_t       sads[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            const uint8_t* ctr     = at_fp(fr, fc);
+            for (int px = l; px < g.npix; px += 64) {
+                int w, k;
+                target(px, w, k);
+                const uint8_t* q = ctr + (int64_t)(px >> g.lw) * rs + (px & (g.W - 1));
+#pragma unroll
+                for (int j = 0; j < 8; j++)
+                    if (in & (1u << j)) {
+                        const int v = (int)((uint32_t)w - (uint32_t)load_px(q + NR[j] * rs + NC[j]) * (uint32_t)k);
+                        sads[j] += ((v < 0 ? 0u - (uint32_t)v : (uint32_t)v) + 2048u) >> 12;
+                    }
+            }
+            int best_site = -1;
+#pragma unroll
+            for (int j = 0; j < 8; j++)
+                if (in & (1u << j)) {
+                    uint32_t sad = (uint32_t)wave_sum((int)sads[j]);
+                    evals++;
+                    if (sad < best_sad) {
+                        sad += sad_cost((int16_t)(fr + NR[j]), (int16_t)(fc + NC[j]));
+                        if (sad < best_sad) best_sad = sad, best_site = j;
+                    }
+                }
+            if (best_site == -1) break;
+            fr = (int16_t)(fr + ((0x2894 >> (2 * best_site)) & 3) - 1), fc = (int16_t)(fc + ((0xA61 >> (2 * best_site)) & 3) - 1); // NR / NC as 2-bit fields, value + 1
+            fp_rounds++;
+        }
+        thissme = (int)best_sad;
+        if (thissme < 0x7fffffff) { // get_obmc_mvpred_var
+            reset();
+            pred_full(at_fp(fr, fc), rs, g, l, acc);
+            evals++;
+            thissme = (int)(finish(sse) + err_cost((int16_t)(fr * 8), (int16_t)(fc * 8)));
+        }
+    }
+    int      br = fr * 8, bc = fc * 8;
+    uint32_t besterr = 0, sse1 = 0;
+    int      distortion = 0;
+    if (d.do_frac_refine) { // svt_av1_find_best_obmc_sub_pixel_tree_up (av1me.c:963)
+        const int max_mv = 8 * 1023; // set_subpel_mv_search_range on the un-narrowed limits
+        const int minc = std::max(-MV_UPP_ + 1, std::max(d.lim_col_min * 8, rc - max_mv)), maxc = std::min(MV_UPP_ - 1, std::min(d.lim_col_max * 8, rc + max_mv));
+        const int minr = std::max(-MV_UPP_ + 1, std::max(d.lim_row_min * 8, rr - max_mv)), maxr = std::min(MV_UPP_ - 1, std::min(d.lim_row_max * 8, rr + max_mv));
+        int       round = 3 - (int)d.forced_stop;
+        if (!d.allow_hp && round == 3) round = 2;
+        reset();
+        pred_full(at_fp(fr, fc), rs, g, l, acc); // either centre form: the upsampled prediction at offset 0, 0 is the copy
+        evals++;
+        besterr    = finish(sse1);
+        distortion = (int)besterr;
+        besterr += err_cost((int16_t)(fr * 8), (int16_t)(fc * 8));
+        int hstep = 4;
+#pragma unroll 1
+        for (int iter = 0; iter < round; iter++) {
+            const int r0 = br, c0 = bc;
+            uint32_t  c_left = 0, c_right = 0, c_up = 0, c_down = 0;
+            int       best_idx = -1, kr = 0, kc = 0, tr = 0, tc = 0, br0 = 0, bc0 = 0;
+            const auto ax_r = [&](const int s) { return s == 2 ? -hstep : (s == 3 ? hstep : 0); }; // search_step_table: left, right, up, down
+            const auto ax_c = [&](const int s) { return s == 0 ? -hstep : (s == 1 ? hstep : 0); };
+#pragma unroll 1
+            for (int step = 0; step < 8; step++) {
+                int r, c;
+                if (step < 4) r = r0 + ax_r(step), c = c0 + ax_c(step);
+                else if (step == 4) {
+                    kc = c_left <= c_right ? -hstep : hstep, kr = c_up <= c_down ? -hstep : hstep;
+                    tc = c0 + kc, tr = r0 + kr;
+                    r = tr, c = tc;
+                } else {
+                    if (step == 5) {
+                        if (best_idx >= 0 && best_idx < 4) br = r0 + ax_r(best_idx), bc = c0 + ax_c(best_idx);
+                        else if (best_idx == 4) br = tr, bc = tc;
+                        if (!(d.iters_per_step > 1 && best_idx != -1)) break;
+                        // SECOND_LEVEL_CHECKS_BEST
+                        if (tr == br && tc != bc) kc = bc - tc;
+                        else if (tr != br && tc == bc) kr = br - tr;
+                        br0 = br, bc0 = bc;
+                        r = br0 + kr, c = bc0;
+                    } else if (step == 6) r = br0, c = bc0 + kc;
+                    else {
+                        if (br0 == br && bc0 == bc) break;
+                        r = br0 + kr, c = bc0 + kc;
+                    }
+                }
+                if (c >= minc && c <= maxc && r >= minr && r <= maxr) {
+                    reset();
+                    const uint8_t* p = ref + (int64_t)(r >> 3) * rs + (c >> 3);
+                    if (d.subpel_search_type == 0) pred_bil(p, rs, c & 7, r & 7, g, l, acc);
+                    else pred_up(p, rs, c & 7, r & 7, d.subpel_search_type, g, im, l, acc);
+                    const uint32_t thismse = finish(sse);
+                    evals++;
+                    const uint32_t tot = err_cost((int16_t)r, (int16_t)c) + thismse;
+                    if (tot < besterr) {
+                        besterr = tot, distortion = (int)thismse, sse1 = sse;
+                        if (step < 5) best_idx = step;
+                        else br = r, bc = c;
+                    }
+                    if (step == 0) c_left = tot;
+                    else if (step == 1) c_right = tot;
+                    else if (step == 2) c_up = tot;
+                    else if (step == 3) c_down = tot;
+                } else if (step == 0) c_left = 0x7fffffffu; // INT_MAX
+                else if (step == 1) c_right = 0x7fffffffu;
+                else if (step == 2) c_up = 0x7fffffffu;
+                else if (step == 3) c_down = 0x7fffffffu;
+            }
+            hstep >>= 1;
+        }
+    }
+    if (l == 0) {
+        const int16_t mr = (int16_t)br, mc = (int16_t)bc;
+        int           rate;
+        if (d.approx_inter_rate) rate = (int)light(abs((int)mc - rc), abs((int)mr - rr)); // svt_av1_mv_bit_cost_light
+        else if (!tab) rate = 0;
+        else { // svt_av1_mv_bit_cost, MV_COST_WEIGHT 108
+            const int16_t dr = (int16_t)(mr - rr), dc = (int16_t)(mc - rc);
+            rate             = (int)((uint32_t)tab_cost(dr, dc) * 108u + 64u) >> 7;
+        }
+        SvtHipObmcSearchResult r;
+        r.mv_row = mr, r.mv_col = mc, r.fp_row = fr, r.fp_col = fc, r.thissme = thissme, r.besterr = besterr, r.distortion = distortion, r.sse1 = sse1, r.rate_mv = rate;
+        r.fp_rounds = fp_rounds, r.evals = evals;
+        out[item] = r;
+    }
+}
+__global__ __launch_bounds__(256) void obmc_search_check_kernel(const SvtHipInterPredPlanes planes, const bool have_src, const bool have_arrays, const bool have_tables,
+                                                                const uint32_t n_tables, const SvtHipObmcSearchDesc* __restrict__ descs, const uint32_t n,
+                                                                uint32_t* __restrict__ bad_out) {
+    bool bad = false;
+    for (uint32_t i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) bad |= !obmc_search_desc_ok(descs[i], planes, have_src, have_arrays, have_tables, n_tables);
+    if (bad) *bad_out = 1;
+}
+
 // descriptors the host cannot read: one word says whether any is invalid (the contract of svt_hip_inter_pred_batch)
 template <typename F> bool any_invalid(const uint32_t n, hipStream_t st, F&& launch_check) {
     svthip::HostCall& c = svthip::host_call();
@@ -595,6 +955,151 @@ int svt_hip_md_subpel_mv_limits(int mi_row, int mi_col, int bsize, int mi_rows, 
     limits[1] = std::min(MV_UPP_ - 1, std::min(col_max * 8, ref_mv_col + max_mv));
     limits[2] = std::max(-MV_UPP_ + 1, std::max(row_min * 8, ref_mv_row - max_mv));
     limits[3] = std::min(MV_UPP_ - 1, std::min(row_max * 8, ref_mv_row + max_mv));
+    return 0;
+}
+
+int svt_hip_obmc_wsrc_batch(SvtHipInterPredPlanes planes, const uint8_t* src_base, const SvtHipObmcWsrcDesc* descs, uint32_t n, int32_t* wsrc_out, int32_t* mask_out,
+                            uint8_t* status, void* stream) {
+    if (n == 0) return 0;
+    if (!src_base || !descs || !wsrc_out || !mask_out) return -1;
+    if (svthip::failed()) return SVT_HIP_E_DEVICE;
+    SVT_HIP_ENTRY_TRY
+    svthip::ensure_device();
+    hipStream_t st = (hipStream_t)stream;
+    if (!status &&
+        any_invalid(n, st, [&](dim3 grid, uint32_t* bad) { hipLaunchKernelGGL(obmc_wsrc_check_kernel, grid, dim3(256), 0, st, planes, descs, n, bad); }))
+        return -1;
+    hipLaunchKernelGGL(obmc_wsrc_kernel, dim3(n), dim3(256), 0, st, planes, src_base, descs, n, wsrc_out, mask_out, status);
+    SVT_LAUNCH_CHECK();
+    SVT_HIP_ENTRY_CATCH(SVT_HIP_E_DEVICE)
+    return 0;
+}
+
+int svt_hip_obmc_search_batch(SvtHipInterPredPlanes planes, const uint8_t* src_base, const int32_t* wsrc_base, const int32_t* mask_base, const SvtHipMvCostTable* tables,
+                              uint32_t n_tables, const SvtHipObmcSearchDesc* descs, uint32_t n, SvtHipObmcSearchResult* out, uint8_t* status, void* stream) {
+    if (n == 0) return 0;
+    if (!descs || !out) return -1;
+    if (svthip::failed()) return SVT_HIP_E_DEVICE;
+    SVT_HIP_ENTRY_TRY
+    svthip::ensure_device();
+    hipStream_t st       = (hipStream_t)stream;
+    const bool  have_src = src_base != nullptr, have_arrays = wsrc_base != nullptr && mask_base != nullptr;
+    if (!status && any_invalid(n, st, [&](dim3 grid, uint32_t* bad) {
+            hipLaunchKernelGGL(obmc_search_check_kernel, grid, dim3(256), 0, st, planes, have_src, have_arrays, tables != nullptr, n_tables, descs, n, bad);
+        }))
+        return -1;
+    launch_classes(
+        [&](const bool big, const dim3 grid, const dim3 block) {
+            if (big)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(obmc_search_kernel<true>), grid, block, OBMC_LDS_BIG, st, planes, src_base, wsrc_base, mask_base, tables, n_tables, descs, n,
+                                   out, status);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(obmc_search_kernel<false>), grid, block, OBMC_LDS_SMALL, st, planes, src_base, wsrc_base, mask_base, tables, n_tables, descs,
+                                   n, out, status);
+            SVT_LAUNCH_CHECK();
+        },
+        n);
+    SVT_HIP_ENTRY_CATCH(SVT_HIP_E_DEVICE)
+    return 0;
+}
+
+int svt_hip_obmc_mv_limits(int mi_row, int mi_col, int bsize, int mi_rows, int mi_cols, int32_t* limits) {
+    if (bsize < 0 || bsize >= 22 || !limits) return -1;
+    const int mi_w = hBw[bsize] >> 2, mi_h = hBh[bsize] >> 2; // single_motion_search :2322-2327 (MI_SIZE 4, AOM_INTERP_EXTEND 4)
+    limits[0] = -(((mi_col + mi_w) * 4) + 4);
+    limits[1] = (mi_cols - mi_col) * 4 + 4;
+    limits[2] = -(((mi_row + mi_h) * 4) + 4);
+    limits[3] = (mi_rows - mi_row) * 4 + 4;
+    return 0;
+}
+
+int svt_hip_obmc_refine_host(const SvtHipObmcSearchDesc* desc, const uint8_t* ref, int ref_stride, int ref_border, const int32_t* wsrc, const int32_t* mask,
+                             const uint8_t* src, int src_stride, const uint8_t* above, int above_stride, const uint8_t* left, int left_stride,
+                             const SvtHipMvCostTable* table, SvtHipObmcSearchResult* result) {
+    if (!desc || !ref || !result || ref_border < 0) return -1;
+    SvtHipObmcSearchDesc d = *desc;
+    if (d.bsize >= 22 || hBw[d.bsize] < 8 || hBh[d.bsize] < 8 || d.target_form > SVT_HIP_OBMC_TARGET_DERIVED || d.fpel_search_range > 64) return -1;
+    const bool derived = d.target_form == SVT_HIP_OBMC_TARGET_DERIVED;
+    if (derived ? !src : (!wsrc || !mask)) return -1;
+    if (svthip::failed()) return SVT_HIP_E_DEVICE;
+    const size_t W = hBw[d.bsize], H = hBh[d.bsize], blk = W * H, ovA = std::min<size_t>(H, 64) >> 1, ovL = std::min<size_t>(W, 64) >> 1;
+    {   // the start vector as the kernel derives it, and how far a search can move from it
+        int sr = d.best_pred_mv_row >> 3, sc = d.best_pred_mv_col >> 3;
+        if (d.do_full_refine) {
+            const int rr = d.ref_mv_row, rc = d.ref_mv_col;
+            const int cmin = std::max(d.lim_col_min, std::max((rc >> 3) - 1023 + ((rc & 7) ? 1 : 0), (-MV_UPP_ >> 3) + 1));
+            const int rmin = std::max(d.lim_row_min, std::max((rr >> 3) - 1023 + ((rr & 7) ? 1 : 0), (-MV_UPP_ >> 3) + 1));
+            const int cmax = std::min(d.lim_col_max, std::min((rc >> 3) + 1023, (MV_UPP_ >> 3) - 1));
+            const int rmax = std::min(d.lim_row_max, std::min((rr >> 3) + 1023, (MV_UPP_ >> 3) - 1));
+            sc = (int16_t)(sc < cmin ? cmin : (sc > cmax ? cmax : sc)), sr = (int16_t)(sr < rmin ? rmin : (sr > rmax ? rmax : sr));
+        }
+        const int need = std::max(std::abs(sr), std::abs(sc)) + (d.do_full_refine ? (int)d.fpel_search_range : 0) + (d.do_frac_refine ? 6 : 0);
+        if (need > ref_border) return -1;
+    }
+    SVT_HIP_ENTRY_TRY
+    const size_t b = (size_t)ref_border, rw = W + 2 * b, rh = H + 2 * b;
+    const size_t bytes = rw * rh + (derived ? blk + W * ovA + H * ovL : blk * 8) + (table ? sizeof(SvtHipMvCostTable) : 0) + sizeof(d) + 64 + 8 * 256;
+    svthip::HostCall& c = svthip::host_call();
+    c.begin();
+    c.reserve(bytes, bytes);
+    uint8_t* dref = (uint8_t*)c.dalloc(rw * rh);
+    c.up2d(dref, rw, ref - (ptrdiff_t)b * ref_stride - (ptrdiff_t)b, (size_t)ref_stride, rw, rh);
+    SvtHipInterPredPlanes planes{};
+    planes.base[0] = dref;
+    d.ref_plane = 0, d.ref_off = b * rw + b, d.ref_stride = (uint32_t)rw, d.above_plane = 1, d.left_plane = 2;
+    uint8_t* dsrc = nullptr;
+    int32_t *dws = nullptr, *dmk = nullptr;
+    if (derived) {
+        dsrc = (uint8_t*)c.dalloc(blk);
+        c.up2d(dsrc, W, src, (size_t)src_stride, W, H);
+        d.src_off = 0, d.src_stride = (uint32_t)W;
+        if (above && d.up_available && d.n_above) {
+            uint8_t* da = (uint8_t*)c.dalloc(W * ovA);
+            c.up2d(da, W, above, (size_t)above_stride, W, ovA);
+            planes.base[1] = da, d.above_off = 0, d.above_stride = (uint32_t)W;
+        }
+        if (left && d.left_available && d.n_left) {
+            uint8_t* dl = (uint8_t*)c.dalloc(H * ovL);
+            c.up2d(dl, ovL, left, (size_t)left_stride, ovL, H);
+            planes.base[2] = dl, d.left_off = 0, d.left_stride = (uint32_t)ovL;
+        }
+    } else {
+        dws = (int32_t*)c.dalloc(blk * 4), dmk = (int32_t*)c.dalloc(blk * 4);
+        c.up(dws, wsrc, blk * 4);
+        c.up(dmk, mask, blk * 4);
+        d.wsrc_off = d.mask_off = 0;
+    }
+    SvtHipMvCostTable* dt = nullptr;
+    if (table) {
+        dt = (SvtHipMvCostTable*)c.dalloc(sizeof(SvtHipMvCostTable));
+        c.up(dt, table, sizeof(SvtHipMvCostTable));
+    }
+    d.cost_table = table ? 0 : -1;
+    SvtHipObmcSearchDesc* dd = (SvtHipObmcSearchDesc*)c.dalloc(sizeof(d));
+    c.up(dd, &d, sizeof(d));
+    uint8_t* dres = (uint8_t*)c.dalloc(64); // the result, and at byte 52 the check kernel's word
+    uint8_t  back[64];
+    memset(back, 0, sizeof(back));
+    c.up(dres, back, sizeof(back));
+    // one item: only the launch class of its size
+    if (blk > (size_t)SMALL_PIX)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(obmc_search_kernel<true>), dim3(1), dim3(64), OBMC_LDS_BIG, c.stream, planes, (const uint8_t*)dsrc, (const int32_t*)dws,
+                           (const int32_t*)dmk, (const SvtHipMvCostTable*)dt, table ? 1u : 0u, (const SvtHipObmcSearchDesc*)dd, 1u, (SvtHipObmcSearchResult*)dres,
+                           (uint8_t*)nullptr);
+    else
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(obmc_search_kernel<false>), dim3(1), dim3(64 * SMALL_WAVES), OBMC_LDS_SMALL, c.stream, planes, (const uint8_t*)dsrc,
+                           (const int32_t*)dws, (const int32_t*)dmk, (const SvtHipMvCostTable*)dt, table ? 1u : 0u, (const SvtHipObmcSearchDesc*)dd, 1u,
+                           (SvtHipObmcSearchResult*)dres, (uint8_t*)nullptr);
+    SVT_LAUNCH_CHECK();
+    hipLaunchKernelGGL(obmc_search_check_kernel, dim3(1), dim3(256), 0, c.stream, planes, dsrc != nullptr, dws != nullptr, dt != nullptr, table ? 1u : 0u,
+                       (const SvtHipObmcSearchDesc*)dd, 1u, (uint32_t*)(dres + 52));
+    SVT_LAUNCH_CHECK();
+    c.down(back, dres, sizeof(back));
+    uint32_t bad;
+    memcpy(&bad, back + 52, 4);
+    if (bad) return -1;
+    memcpy(result, back, sizeof(*result));
+    SVT_HIP_ENTRY_CATCH(SVT_HIP_E_DEVICE)
     return 0;
 }
 
